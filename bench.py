@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: 64-bit Borromean rangeproof verifies/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1: starts the N ranks itself, one per GPU, through the line below)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                               (N > 1: starts the N ranks itself, one per GPU, through the line below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = one pass of the verification hot path (secp256k1_rangeproof_verify semantics, five HIP kernels) over one batch
 of 2^14 synthetic 64-bit proofs per GPU (BASELINE.json configs[2]; the batch the metric is quoted on), inputs already
 resident in HBM.  Independent proofs shard with no exchange step, so N GPUs run N replicas of the batch ("weak" scaling).
-One JSON line is printed by rank 0.  Also reported: the roofline of the dominant kernel (k_rp_rings) and the reference's
-own CPU path timed on the host cores of the same box (oracle/_ref, bounded sample).
+One JSON line is printed by rank 0.  A plain run sets up, warms up (W steps), times K steps and prints the headline
+(value, ms_per_step); --dump-outputs DIR also writes the last timed step's verdicts and min / max values to DIR/*.npy.
+Only --full reports the rest: the roofline of the dominant kernel (k_rp_rings), the same batch with serialized calls, with
+distinct generators, through host memory and at narrower tables, the MSM, the secondary configs, the engine group and the
+reference's own CPU path timed on the host cores of the same box (oracle/_ref, bounded sample).
 """
 import argparse
 import glob
@@ -746,6 +750,25 @@ def cpu_baseline(ref, commits, proofs, gens):
             "sample": "%d 64-bit proofs on %d threads (%.2f s) = %.0f verifies/s; single thread: %d proofs in %.2f s = %.1f verifies/s per core (the reference is single-threaded; cores = cgroup CPU quota of the box)" % (kn, cores, tn, kn / tn, k1, t1, k1 / t1)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, min_value, max_value):
+    """--dump-outputs: the headline's per-proof results (int32 verdicts, uint64 min / max values) as DIR/verdict.npy (float32),
+    DIR/min_value.npy and DIR/max_value.npy (float64).  A batch whose three arrays exceed 64 MB is cut to a fixed, seeded sample of
+    proofs, whose indices go to DIR/sample_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = res.shape[0]
+    per_item = 4 + 8 + 8
+    if n * per_item > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, (DUMP_MAX_BYTES - 8 * 1024) // (per_item + 8), replace=False))
+        res, min_value, max_value = res[idx], min_value[idx], max_value[idx]
+        np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "verdict.npy"), res.astype(np.float32))
+    np.save(os.path.join(out_dir, "min_value.npy"), min_value.astype(np.float64))
+    np.save(os.path.join(out_dir, "max_value.npy"), max_value.astype(np.float64))
+
+
 def main():
     t_process = time.time()
     ap = argparse.ArgumentParser()
@@ -763,6 +786,9 @@ def main():
     ap.add_argument("--no-widths", action="store_true", help="skip the headline at 24- and 20-bit fixed-base tables")
     ap.add_argument("--no-next", action="store_true", help="skip the SURVEY 8(f) rows (surjection, half-aggregate, tallies, rewind, bppp_commit, batched small sums)")
     ap.add_argument("--rp-split", type=int, choices=(0, 1), default=None, help="S2K_OPT_RP_SPLIT of the engine (A/B of the two forms of the ring kernel's double multiplication: tools/profile_mem_counters.sh)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (serialized calls and roofline, distinct generators, drop-in path, "
+                                                        "MSM, secondary configs, engine group, table widths, CPU baselines); the --no-* options above select among these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the headline's last timed step computed (verdicts, min and max values) to DIR/*.npy")
     args = ap.parse_args()
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # the hosts only support dmabuf IPC: RCCL between the ranks fails without it (set here, not at import: tests import this module)
 
@@ -778,14 +804,17 @@ def main():
         sys.exit("bench.py: --gpus %d but this node has %d GPU(s): one rank per GPU over RCCL needs %d devices "
                  "(S2K_DIST_BACKEND=gloo lets ranks share a device, for testing only)" % (args.gpus, torch.cuda.device_count(), args.gpus))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` on its own: become the launcher of N ranks, one per GPU (exactly the command the docstring shows);
-        # rank 0's JSON line goes to this process's stdout.  Under torch.distributed.run (WORLD_SIZE set) this branch is not taken.
-        # (--standalone: the launcher picks its own rendezvous port -- probing for a free one here and handing it over is a race when
-        #  several benches start on one node)
+        # `python bench.py --gpus N` on its own: start the launcher of N ranks, one per GPU (exactly the command the docstring shows), as a
+        # child process and exit with its status; rank 0's JSON line goes to the inherited stdout.  Under torch.distributed.run (WORLD_SIZE
+        # set) this branch is not taken.  (A child, not exec: this process has already initialised the GPU runtime above, and replacing such
+        # a process is not safe.  --standalone: the launcher picks its own rendezvous port -- probing for a free one here and handing it
+        # over is a race when several benches start on one node)
+        import subprocess
         cmd = [sys.executable, "-m", "torch.distributed.run", "--standalone", "--local-addr", "127.0.0.1", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush(); sys.stderr.flush()
-        os.execvpe(cmd[0], cmd, dict(os.environ))
+        rc = subprocess.run(cmd, env=dict(os.environ)).returncode
+        sys.exit(rc if rc >= 0 else 128 - rc)         # (a rank killed by a signal: the shell's 128 + signal)
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         sys.exit("bench.py: --gpus %d but the launcher started %d rank(s) (WORLD_SIZE): the two must agree" % (args.gpus, world))
@@ -869,15 +898,18 @@ def main():
         d = time.perf_counter() - t0
         return d, [eng.last_ms(16 + k) for k in range(min(k_steps, 32))]          # HIP events around the ring kernels on the launch stream
 
+    # --full: the serialized loop first (value_serialized_calls, the ring kernel's undisturbed time for the roofline); a plain run times
+    # only the headline's loop
     ser_steps = max(2, min(args.steps, 10))
-    dt_ser, kern_ms = timed(ser_steps, False)
-    if pipeline:
-        dt, kern_ms_pipe = timed(args.steps, True)
-    else:
-        dt, kern_ms_pipe = timed(args.steps, False)
+    if args.full:
+        dt_ser, kern_ms = timed(ser_steps, False)
+    dt, kern_ms_pipe = timed(args.steps, pipeline)
+    if not pipeline:
         kern_ms = kern_ms_pipe
+    # what the last timed step computed, as its caller receives it (every step writes the same three arrays)
+    h_res, h_min, h_max = d_res.cpu().numpy(), d_min.cpu().numpy().view(np.uint64), d_max.cpu().numpy().view(np.uint64)
     eng.set_option(Engine.OPT_RP_INPUTS_READY, 0)
-    if world > 1:
+    if world > 1 and args.full:
         tser = torch.tensor([dt_ser], dtype=torch.float64, device=dev); dist.all_reduce(tser, op=dist.ReduceOp.MAX); dt_ser = float(tser.item())
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -888,12 +920,14 @@ def main():
         all_ok = bool(d_res.all().item())
     assert all_ok, "a valid proof was rejected"
     assert int(d_max.min().item()) == -1          # max_value == 2^64-1 for every 64-bit proof
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, h_res, h_min, h_max)
 
     # The same batch size with a DIFFERENT generator for every proof (the Elements case: one blinded asset generator per confidential
     # output).  No fixed-base generator table applies there (secp256k1_zkp_amd.h, s2k_engine_cache_generator), so every ring takes the
     # general form of the rings kernel: reported next to the headline so that the shared-generator figure cannot be misread.
     distinct = None
-    if not args.no_distinct and ref is not None:
+    if args.full and not args.no_distinct and ref is not None:
         c2, p2, g2, _, _ = make_inputs(n, seed=4321 + rank, distinct_generators=True)
         pd2, po2 = Engine.pack(p2)
         d_c2 = torch.tensor(c2).to(dev); d_g2 = torch.tensor(np.ascontiguousarray(g2)).to(dev)
@@ -921,14 +955,14 @@ def main():
     # secp256k1_amd_rangeproof_verify_batch of libsecp256k1_hooked.so (the unmodified reference + integration/secp256k1_amd_hook.c) with the
     # reference's own types -- arrays of pointers to secp256k1_pedersen_commitment / secp256k1_generator objects and to the proofs.
     dropin = None
-    if rank == 0 and not args.no_dropin:
+    if args.full and rank == 0 and not args.no_dropin:
         dropin = measure_dropin(eng, commits, proofs, gens, steps=max(3, min(args.steps, 5)))
         dropin["resident_verifies_per_s"] = n * args.steps / dt
 
     # secondary figure of the BASELINE metric: one 2^20-term MSM (config 5), terms sharded over the ranks, partial
     # Jacobian sums all-gathered as raw limbs (RCCL) and summed locally -- strong scaling, reported next to the headline.
     msm = None
-    if not args.no_msm:
+    if args.full and not args.no_msm:
         # (the loops above leave the board at its power limit; a different workload is timed from an idle board, as a caller would meet it)
         torch.cuda.synchronize(); time.sleep(1.0)
         from secp256k1_zkp_amd import parallel
@@ -1070,7 +1104,7 @@ def main():
     # BASELINE configs 2 and 4 (and config 1's GPU side): same conventions as the headline -- inputs made by the reference, resident in HBM,
     # K stream-ordered `_dev` calls queued back to back and waited for once, every verdict checked in-run against the reference's.
     secondary = None
-    if rank == 0 and not args.no_secondary and ref is not None:
+    if args.full and rank == 0 and not args.no_secondary and ref is not None:
         torch.cuda.synchronize(); time.sleep(1.0)
         secondary = measure_secondary(eng, ref, dev, max(3, args.steps), with_cpu=not args.no_cpu_baseline)
         if not args.no_next:
@@ -1083,7 +1117,7 @@ def main():
     # run through s2k_group_* -- the path a C caller without torch.distributed takes.  With one GPU: two engines on it (they share the
     # device's tables), which shows what a second submitting thread buys on a single device.
     group = None
-    if not args.no_group:
+    if args.full and not args.no_group:
         if world > 1:
             dist.barrier()
         if rank == 0:
@@ -1100,7 +1134,7 @@ def main():
     # 26): the same timed loop after the device's tables have been given back and rebuilt at that width -- what an engine on a partitioned or
     # shared GPU gets.  Verdicts are checked again; the default width is restored afterwards.
     width_values = None
-    if rank == 0 and world == 1 and not args.no_widths:
+    if args.full and rank == 0 and world == 1 and not args.no_widths:
         width_values = {}
         try:
             for bits in (24, 20):
@@ -1117,45 +1151,6 @@ def main():
 
     if rank == 0:
         value = world * n * args.steps / dt
-        kms = float(np.mean(kern_ms))
-        achieved = PROOF_BYTES_ALGO * n / (kms * 1e-3) / 1e9
-        # memory-side traffic and issued-instruction counters of the dominant kernel: PMC counters cannot be read from inside this process,
-        # so the figures are committed rocprofv3 passes of this same command (profiles/, tools/profile_round.sh) -- used ONLY when the file
-        # carries the sha256 of the library this process has loaded (the counters then belong to this binary); otherwise null + the reason
-        import hashlib
-        from secp256k1_zkp_amd import _native
-        lib_sha = hashlib.sha256(open(_native.LIB_PATH, "rb").read()).hexdigest()
-        # (hipcc's output is not reproducible byte for byte -- two builds of one source tree differ in the offload bundle's ids -- so a file
-        #  also counts when it carries the sha256 of the library's SOURCES, csrc/* + the public header, as they are in this tree)
-        src_sha = _native.sources_sha256()
-        traffic, traffic_src, issued = None, None, None
-        def _stamped(pattern):
-            for f in sorted(glob.glob(os.path.join(ROOT, "profiles", pattern)), reverse=True):
-                try:
-                    j = json.load(open(f))
-                except Exception:
-                    continue
-                if j.get("so_sha256") == lib_sha or (src_sha and j.get("src_sha256") == src_sha):
-                    return f, j
-            return None, None
-        f_pmc, pj = _stamped("*pmc_rp_rings.json")
-        if pj:
-            traffic = pj["hbm_bytes_per_launch_raw"] * n / 16384.0
-            traffic_src = os.path.relpath(f_pmc, ROOT) + (" (same library binary)" if pj.get("so_sha256") == lib_sha else " (same library sources, another build)")
-        else:
-            traffic_src = "no profiles/*pmc_rp_rings.json stamped with this library's sha256 (%s...): run tools/profile_round.sh on this build" % lib_sha[:12]
-        # issued (not algorithmic) integer-MAC rate: SQ counter passes of this same command; SQ_INSTS_VALU_INT64 counts wave-level 64-bit
-        # integer instructions (v_mad_u64_u32 and the 64-bit shifts)
-        f_sq, sj = _stamped("*sq_counters.json")
-        if sj:
-            kname = "k_rp_rings_shared" if "k_rp_rings_shared" in sj else "k_rp_rings"
-            cj = sj.get(kname, {})
-            if "SQ_INSTS_VALU_INT64" in cj:
-                int64 = cj["SQ_INSTS_VALU_INT64"]["mean_per_launch"] * n / 16384.0; valu = cj["SQ_INSTS_VALU"]["mean_per_launch"] * n / 16384.0
-                issued = {"source": os.path.relpath(f_sq, ROOT), "kernel": kname, "int64_wave_instructions_per_launch": int64, "valu_wave_instructions_per_launch": valu,
-                          "int64_lane_ops_per_s": int64 * 64 / (kms * 1e-3), "frac_of_peak": int64 * 64 / (kms * 1e-3) / MAD32_PEAK,
-                          "note": "counter-backed issue rate of 64-bit integer VALU instructions (v_mad_u64_u32 + 64-bit shifts) in the rings kernel, this run's kernel time"}
-        mad_rate = 4 * MAC64_PER_PROOF * n / (kms * 1e-3)
         out = {
             "metric": "64-bit Borromean rangeproof verifies/sec", "value": value, "unit": "verifies/s", "n_gpus": world,
             # the exchange library's own view of the job: world size after a checked all-reduce ("rccl" when the backend is nccl), the device of every rank
@@ -1166,32 +1161,74 @@ def main():
             "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs (9x29-bit), 32x32->64 integer MAC", "data": data_desc,
             # verified: every timed proof was signed by the reference (oracle/_ref) and accepted; false when the run fell back to a tiled golden proof
             "verified": ref is not None,
-            "value_serialized_calls": world * n * ser_steps / dt_ser, "ms_per_step_serialized_calls": dt_ser / ser_steps * 1e3,
-            "value_distinct_generators": distinct["value"] if distinct else None,
-            "value_gtab_bits_24": width_values.get(24, {}).get("value") if width_values else None,
-            "value_gtab_bits_20": width_values.get(20, {}).get("value") if width_values else None,
-            "table_widths": width_values,
-            "ms_per_step_distinct_generators": distinct["ms_per_step"] if distinct else None,
-            "generators": "value: secp256k1_generator_h for every proof (src/bench_rangeproof.c), fixed-base table of that generator cached by the engine; "
-                          "value_distinct_generators: the same batch size, every proof its own random generator (no table applies: general form of the rings kernel)",
             "config": {"workload": "secp256k1_rangeproof_verify, batch of %d 64-bit proofs per GPU (exp=0, min_value=0, 32 rings x 4)" % n,
                        "batch_per_gpu": n, "sharding": "replicas (independent proofs, no collective)",
                        "calls_in_flight": ("K steps queued back to back, first stage of step k+1 on side streams under step k's ring kernel "
                                            "(S2K_OPT_RP_INPUTS_READY: inputs resident and untouched)") if pipeline
                                           else "same queueing, engine default: the first stage of a call waits for the call before it"},
-            # the binding roofline of this path is the integer VALU: exact 256-bit modular arithmetic, no MFMA, ~0.05 % of HBM
-            "roofline": {"bound": "valu", "kernel": "k_rp_rings_shared (+ k_rp_rings for wavefronts without a generator table)", "achieved": mad_rate / 1e12, "peak": MAD32_PEAK / 1e12,
-                         "unit": "T lane-MAC/s (v_mad_u64_u32, 32x32+64)", "frac": mad_rate / MAD32_PEAK, "frac_of_architectural_peak": mad_rate / MAD32_PEAK_ARCH,
-                         "traffic": traffic, "traffic_unit": "HBM-side bytes per launch (FETCH_SIZE + WRITE_SIZE, incl. Infinity-Cache hits)", "traffic_source": traffic_src,
-                         "kernel_ms": kms, "kernel_ms_with_calls_in_flight": float(np.mean(kern_ms_pipe)), "issued": issued, "library_sha256": lib_sha, "library_sources_sha256": src_sha,
-                         "note": "achieved = algorithmic 6.6e6 MAC64/proof (reference schedule, SURVEY 8d) x 4 v_mad_u64_u32 x proofs / kernel time (HIP events on the launch stream); "
-                                 "peak measured with >= 10 ms launches (tools/ubench/issue_model.hip, profiles/r02a_issue_model.txt)"},
-            "hbm_roofline": {"bound": "hbm", "kernel": "k_rp_rings_shared + k_rp_rings", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                             "algorithmic_bytes": PROOF_BYTES_ALGO * n, "note": "reported because the contract asks; not the binding bound"},
         }
+        if args.full:
+            kms = float(np.mean(kern_ms))
+            achieved = PROOF_BYTES_ALGO * n / (kms * 1e-3) / 1e9
+            # memory-side traffic and issued-instruction counters of the dominant kernel: PMC counters cannot be read from inside this process,
+            # so the figures are committed rocprofv3 passes of this same command (profiles/, tools/profile_round.sh) -- used ONLY when the file
+            # carries the sha256 of the library this process has loaded (the counters then belong to this binary); otherwise null + the reason
+            import hashlib
+            from secp256k1_zkp_amd import _native
+            lib_sha = hashlib.sha256(open(_native.LIB_PATH, "rb").read()).hexdigest()
+            # (hipcc's output is not reproducible byte for byte -- two builds of one source tree differ in the offload bundle's ids -- so a file
+            #  also counts when it carries the sha256 of the library's SOURCES, csrc/* + the public header, as they are in this tree)
+            src_sha = _native.sources_sha256()
+            traffic, traffic_src, issued = None, None, None
+            def _stamped(pattern):
+                for f in sorted(glob.glob(os.path.join(ROOT, "profiles", pattern)), reverse=True):
+                    try:
+                        j = json.load(open(f))
+                    except Exception:
+                        continue
+                    if j.get("so_sha256") == lib_sha or (src_sha and j.get("src_sha256") == src_sha):
+                        return f, j
+                return None, None
+            f_pmc, pj = _stamped("*pmc_rp_rings.json")
+            if pj:
+                traffic = pj["hbm_bytes_per_launch_raw"] * n / 16384.0
+                traffic_src = os.path.relpath(f_pmc, ROOT) + (" (same library binary)" if pj.get("so_sha256") == lib_sha else " (same library sources, another build)")
+            else:
+                traffic_src = "no profiles/*pmc_rp_rings.json stamped with this library's sha256 (%s...): run tools/profile_round.sh on this build" % lib_sha[:12]
+            # issued (not algorithmic) integer-MAC rate: SQ counter passes of this same command; SQ_INSTS_VALU_INT64 counts wave-level 64-bit
+            # integer instructions (v_mad_u64_u32 and the 64-bit shifts)
+            f_sq, sj = _stamped("*sq_counters.json")
+            if sj:
+                kname = "k_rp_rings_shared" if "k_rp_rings_shared" in sj else "k_rp_rings"
+                cj = sj.get(kname, {})
+                if "SQ_INSTS_VALU_INT64" in cj:
+                    int64 = cj["SQ_INSTS_VALU_INT64"]["mean_per_launch"] * n / 16384.0; valu = cj["SQ_INSTS_VALU"]["mean_per_launch"] * n / 16384.0
+                    issued = {"source": os.path.relpath(f_sq, ROOT), "kernel": kname, "int64_wave_instructions_per_launch": int64, "valu_wave_instructions_per_launch": valu,
+                              "int64_lane_ops_per_s": int64 * 64 / (kms * 1e-3), "frac_of_peak": int64 * 64 / (kms * 1e-3) / MAD32_PEAK,
+                              "note": "counter-backed issue rate of 64-bit integer VALU instructions (v_mad_u64_u32 + 64-bit shifts) in the rings kernel, this run's kernel time"}
+            mad_rate = 4 * MAC64_PER_PROOF * n / (kms * 1e-3)
+            out.update({
+                "value_serialized_calls": world * n * ser_steps / dt_ser, "ms_per_step_serialized_calls": dt_ser / ser_steps * 1e3,
+                "value_distinct_generators": distinct["value"] if distinct else None,
+                "value_gtab_bits_24": width_values.get(24, {}).get("value") if width_values else None,
+                "value_gtab_bits_20": width_values.get(20, {}).get("value") if width_values else None,
+                "table_widths": width_values,
+                "ms_per_step_distinct_generators": distinct["ms_per_step"] if distinct else None,
+                "generators": "value: secp256k1_generator_h for every proof (src/bench_rangeproof.c), fixed-base table of that generator cached by the engine; "
+                              "value_distinct_generators: the same batch size, every proof its own random generator (no table applies: general form of the rings kernel)",
+                # the binding roofline of this path is the integer VALU: exact 256-bit modular arithmetic, no MFMA, ~0.05 % of HBM
+                "roofline": {"bound": "valu", "kernel": "k_rp_rings_shared (+ k_rp_rings for wavefronts without a generator table)", "achieved": mad_rate / 1e12, "peak": MAD32_PEAK / 1e12,
+                             "unit": "T lane-MAC/s (v_mad_u64_u32, 32x32+64)", "frac": mad_rate / MAD32_PEAK, "frac_of_architectural_peak": mad_rate / MAD32_PEAK_ARCH,
+                             "traffic": traffic, "traffic_unit": "HBM-side bytes per launch (FETCH_SIZE + WRITE_SIZE, incl. Infinity-Cache hits)", "traffic_source": traffic_src,
+                             "kernel_ms": kms, "kernel_ms_with_calls_in_flight": float(np.mean(kern_ms_pipe)), "issued": issued, "library_sha256": lib_sha, "library_sources_sha256": src_sha,
+                             "note": "achieved = algorithmic 6.6e6 MAC64/proof (reference schedule, SURVEY 8d) x 4 v_mad_u64_u32 x proofs / kernel time (HIP events on the launch stream); "
+                                     "peak measured with >= 10 ms launches (tools/ubench/issue_model.hip, profiles/r02a_issue_model.txt)"},
+                "hbm_roofline": {"bound": "hbm", "kernel": "k_rp_rings_shared + k_rp_rings", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                                 "algorithmic_bytes": PROOF_BYTES_ALGO * n, "note": "reported because the contract asks; not the binding bound"},
+            })
         # where the wall clock of this process goes: the headline's timed region is a fraction of a second inside a run of tens of seconds
         # (input signing by the reference, table builds, the CPU baselines) -- a GPU-busy sampler around the whole process sees mostly idle
-        out["timing"] = {"timed_region_s": dt, "timed_region_serialized_calls_s": dt_ser, "timed_steps": args.steps,
+        out["timing"] = {"timed_region_s": dt, "timed_region_serialized_calls_s": dt_ser if args.full else None, "timed_steps": args.steps,
                          "process_wall_s_until_headline": time.time() - t_process}
         out["tables"] = tables
         if msm:
@@ -1203,7 +1240,7 @@ def main():
             out["secondary"] = secondary
         if group:
             out["group"] = group
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # (1) the reference's own bench programs (src/bench_rangeproof.c with min_bits = 64, src/bench_ecmult.c; timer of src/bench.h),
             #     one process and one taskset-pinned process per usable core; (2) the same functions through the oracle/_ref shim with
             #     OpenMP, on THIS run's proofs, as a cross-check of (1)

@@ -12,7 +12,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "1", "--warmup", "1", "--batch", "512", "--no-cpu-baseline", "--no-dropin", "--no-distinct"]
+COMMON = ["--full", "--steps", "1", "--warmup", "1", "--batch", "512", "--no-cpu-baseline", "--no-dropin", "--no-distinct"]
 
 
 def _run(world, sharding=None, port=29517, self_launch=False):

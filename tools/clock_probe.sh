@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r02f; mkdir -p $O
-timeout 400 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_INT32 SQ_WAIT_INST_ANY SQ_WAIT_ANY --kernel-trace --output-format csv -d $O/pmc -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-msm > $O/bench_pmc.json 2>$O/pmc.err
+timeout 400 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_INT32 SQ_WAIT_INST_ANY SQ_WAIT_ANY --kernel-trace --output-format csv -d $O/pmc -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-msm > $O/bench_pmc.json 2>$O/pmc.err
 cd $R
 python - <<'PY'
 import csv, glob, collections
