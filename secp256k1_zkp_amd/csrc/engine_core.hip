@@ -623,14 +623,6 @@ extern "C" int s2k_engine_rp_handback(s2k_engine* e, uint32_t out[4]) {
     }
     return 1;
 }
-#ifdef S2K_PROF
-// diagnostic builds only: read (and clear) the per-region cycle table of s2k_common.h
-extern "C" __attribute__((visibility("default"))) int s2k_prof_read(unsigned long long out[16]) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(s2k_prof_slots), 16 * sizeof(unsigned long long)) != hipSuccess) return 0;
-    unsigned long long z[16] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(s2k_prof_slots), z, sizeof(z)) == hipSuccess;
-}
-#endif
 extern "C" float s2k_engine_last_ms(s2k_engine* e, int which) {
     float ms = -1.0f;
     if (!e) return ms;

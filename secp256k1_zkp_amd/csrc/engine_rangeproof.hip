@@ -781,3 +781,12 @@ extern "C" int secp256k1_surjectionproof_verify_batch(s2k_engine* e, int32_t* re
     HIPCHK(hipStreamSynchronize(st));
     return 1;
 }
+#ifdef S2K_PROF
+// diagnostic builds only: read (and clear) the per-region cycle table of s2k_common.h.  Every translation unit has its own copy of the
+// table (no relocatable device code), so the reader lives next to the kernels whose regions it reports: the rings kernels.
+extern "C" __attribute__((visibility("default"))) int s2k_prof_read(unsigned long long out[16]) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(s2k_prof_slots), 16 * sizeof(unsigned long long)) != hipSuccess) return 0;
+    unsigned long long z[16] = {0};
+    return hipMemcpyToSymbol(HIP_SYMBOL(s2k_prof_slots), z, sizeof(z)) == hipSuccess;
+}
+#endif

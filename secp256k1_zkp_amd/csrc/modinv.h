@@ -38,9 +38,11 @@ struct ds_modulus { int32_t w[DS_LIMBS]; u32 inv; };    // modulus in that form 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define DS_WAVE_ANY(p) (__any(p))
 #define DS_WAVE_ALL(p) (__all(p))
+#define DS_UNIFORM(x) (__builtin_amdgcn_readfirstlane(x))
 #else
 #define DS_WAVE_ANY(p) (p)
 #define DS_WAVE_ALL(p) (p)
+#define DS_UNIFORM(x) (x)
 #endif
 
 S2K_HD int ds_ctz32(u32 x) { return __builtin_ctz(x | 0x80000000u); }         // <= 31 also for x = 0
@@ -65,6 +67,31 @@ S2K_HD int32_t ds_batch(int32_t zeta, u32 f, u32 g, int32_t t[4]) {
         g = act ? g2 : g; q = act ? q2 : q; r = act ? r2 : r;
         zeta = sw ? -zeta - 2 : zeta - act;
         u = (int32_t)((u32)u << act); v = (int32_t)((u32)v << act); left -= act;
+    }
+    t[0] = u; t[1] = v; t[2] = q; t[3] = r;
+    return zeta;
+}
+
+// The same 30 steps when zeta, f and g are the same in every lane (ds_inverse_words<true>): the values live in scalar registers, so
+// the loop is scalar code that branches on its data where ds_batch has to select (no vote, no divergence; ~15 instructions a trip
+// instead of ~50 in the select form).
+S2K_HD int32_t ds_batch_uniform(int32_t zeta, u32 f, u32 g, int32_t t[4]) {
+    int32_t u = 1, v = 0, q = 0, r = 1;
+    int left = DS_BITS;
+    for (;;) {
+        int z = ds_ctz32(g); z = z < left ? z : left;
+        g >>= z; u = (int32_t)((u32)u << z); v = (int32_t)((u32)v << z); zeta -= z; left -= z;
+        if (left <= 0) break;
+        if (zeta < 0) {                                     // swap: (f, g, u, v, q, r) <- (g, (g - f)/2, q, r, q - u, r - v)
+            const u32 f0 = f; const int32_t u0 = u, v0 = v;
+            f = g; u = q; v = r;
+            g = (g - f0) >> 1; q -= u0; r -= v0;
+            zeta = -zeta - 2;
+        } else {
+            g = (g + f) >> 1; q += u; r += v;
+            zeta -= 1;
+        }
+        u = (int32_t)((u32)u << 1); v = (int32_t)((u32)v << 1); left -= 1;
     }
     t[0] = u; t[1] = v; t[2] = q; t[3] = r;
     return zeta;
@@ -102,7 +129,11 @@ S2K_HD void ds_add_multiple(ds_int& r, int32_t c, const ds_modulus md) {
     r.w[DS_LIMBS - 1] = (int32_t)(acc + r.w[DS_LIMBS - 1] + (int64_t)c * md.w[DS_LIMBS - 1]);
 }
 
-// w (8 little-endian 32-bit words, value < m) -> w^-1 mod m (0 for 0)
+// w (8 little-endian 32-bit words, value < m) -> w^-1 mod m (0 for 0).
+// UNIFORM = true: w is the same in every lane of the wavefront (waveinv.h).  The batch kernel then takes the low words of f and g
+// through v_readfirstlane and runs on the scalar unit (ds_batch_uniform); so, as the compiler sees that everything else is uniform
+// too, does ds_apply (s_mul_i32 / s_mul_hi_i32 pairs).
+template <bool UNIFORM = false>
 S2K_HD void ds_inverse_words(u32 o[8], const u32 w[8], const ds_modulus md) {
     ds_int f, g, d, e;
 #pragma unroll
@@ -118,7 +149,8 @@ S2K_HD void ds_inverse_words(u32 o[8], const u32 w[8], const ds_modulus md) {
 #pragma unroll 1
     for (int it = 0; it < DS_BATCHES; it++) {
         int32_t t[4];
-        zeta = ds_batch(zeta, (u32)f.w[0], (u32)g.w[0], t);
+        if (UNIFORM) zeta = ds_batch_uniform(DS_UNIFORM(zeta), (u32)DS_UNIFORM(f.w[0]), (u32)DS_UNIFORM(g.w[0]), t);
+        else zeta = ds_batch(zeta, (u32)f.w[0], (u32)g.w[0], t);
         ds_apply<true>(d, e, t, md);
         ds_apply<false>(f, g, t, md);
         // 590 steps is the worst case; random inputs are through after 501..531 of them (18 batches).  Once g = 0 a further batch leaves f

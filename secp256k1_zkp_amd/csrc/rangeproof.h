@@ -18,6 +18,7 @@
 #pragma once
 #include "gtable.h"
 #include "sha256.h"
+#include "waveinv.h"
 
 #define RP_MAX_RINGS 32
 #define RP_GEJ_WORDS 28
@@ -501,8 +502,9 @@ S2K_HD int rp_ring_suspect(const gej& C, const u32* xmul /* this (exp, ring)'s 3
     return hit;
 }
 // K rings per lane (consecutive rings ring0 .. ring0+K-1 of one proof).  Why several: every ring position ends in a field inversion
-// (to-affine before the point is hashed), ~19 000 instructions of the wavefront whatever its lanes hold, and the K points of a lane
-// share ONE inversion (Montgomery's trick, 3 (K - 1) products).  The K rings of a lane advance position by position: for each position
+// (to-affine before the point is hashed) -- per lane ~19 000 VALU instructions of the wavefront whatever its lanes hold; since the
+// wave-batched form (waveinv.h) one per wavefront: 21 000 fewer VALU and ~19 000 more scalar instructions per position -- and the K
+// points of a lane share ONE inversion (Montgomery's trick, 3 (K - 1) products).  The K rings of a lane advance position by position: for each position
 // j the K multiplications run one after the other (one copy of the code, `q` loop), each result is parked (27 words), then one
 // inversion, then K x (affine, serialise, hash).  What a ring carries from one position to the next -- the challenge e and its ok
 // flag -- is parked next to the point.
@@ -616,7 +618,10 @@ S2K_HD int rp_rings_shared(const rp_rec& rec, const u32* pub28, unsigned char* r
             for (int i = 0; i < 9; i++) { pk(q, i) = R.x.n[i]; pk(q, 9 + i) = R.y.n[i]; pk(q, 18 + i) = R.z.n[i]; }
             pk(q, 36) = (u32)good;
         }
-        // ---- one inversion for the K points (every R is finite here: all additions of the step had operands with different x)
+        // ---- one inversion for the K points (every R is finite here: all additions of the step had operands with different x), and on
+        // the device one for the whole wavefront (waveinv.h: Montgomery's trick across the lanes).  Idle lanes take part: their R is
+        // finite too.  A Z that is 0 mod p cannot come out of a step without an exceptional addition; should one appear all the same,
+        // the wavefront takes the general form.
         {
             fe pre[K], z;
 #pragma unroll
@@ -625,7 +630,8 @@ S2K_HD int rp_rings_shared(const rp_rec& rec, const u32* pub28, unsigned char* r
                 for (int i = 0; i < 9; i++) z.n[i] = pk(q, 18 + i);
                 if (q == 0) pre[0] = z; else fe_mul(pre[q], pre[q - 1], z);
             }
-            fe inv; fe_inv(inv, pre[K - 1]);
+            fe inv;
+            if (!fe_inv_lanes(inv, pre[K - 1])) return RP_SHARED_EXCEPTIONAL;
 #pragma unroll
             for (int q = K - 1; q >= 1; q--) {
 #pragma unroll
