@@ -186,6 +186,33 @@ S2K_API int secp256k1_schnorrsig_verify_batch(s2k_engine* e, int32_t* results, c
 S2K_API int secp256k1_schnorrsig_verify_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* sigs,
                                                   const unsigned char* msgs, size_t msglen, const unsigned char* pubkeys, int pk_format, size_t n);
 
+/* ---- ECDSA batch verification -----------------------------------------------------------------------------------
+ * results[i] = signature_i parses && public key_i parses && secp256k1_ecdsa_verify(ctx, sig_i, msghash32_i, pubkey_i)
+ *                                       (include/secp256k1.h, src/secp256k1.c:498-512, src/ecdsa_impl.h:195-272)
+ * As the reference, a signature with s > n/2 is refused (normalise it first).  msghash32 n*32.
+ * sig_format 0: sigs n*64 compact r|s big-endian (secp256k1_ecdsa_signature_parse_compact: r or s >= n gives 0);
+ *            1: sigs n*64 `secp256k1_ecdsa_signature` opaque objects;
+ *            2: DER signatures back to back, item i = sigs[sig_off[i] .. sig_off[i+1]) (sig_off has n+1 entries, as proof_off
+ *               of the rangeproof calls), accepted and refused exactly as secp256k1_ecdsa_signature_parse_der does.
+ *            sig_off is NULL unless sig_format is 2.
+ * pk_format  0: pubkeys n*33 compressed; 1: n*64 `secp256k1_pubkey` opaque objects (an all-zero x, where the reference calls
+ *            its illegal-argument callback, gives 0); 2: n*65 uncompressed or hybrid (04 / 06 / 07).  Serialised keys follow
+ *            secp256k1_ec_pubkey_parse (src/eckey_impl.h:18-36): an encoding it refuses gives 0. */
+S2K_API int secp256k1_ecdsa_verify_batch(s2k_engine* e, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
+                                         const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format, size_t n);
+S2K_API int secp256k1_ecdsa_verify_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off,
+                                             int sig_format, const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format, size_t n);
+/* ---- ECDSA public-key recovery ------------------------------------------------------------------------------------
+ * results[i] = secp256k1_ecdsa_recover(ctx, &pubkeys_out64[64 i], recoverable signature (sigs64_i, recids[i]), msghash32_i)
+ *                                       (include/secp256k1_recovery.h, src/modules/recovery/main_impl.h:87-157)
+ * sigs64 n*64 compact r|s; recids n bytes, 0..3 (anything else, like r or s >= n, gives 0, as
+ * secp256k1_ecdsa_recoverable_signature_parse_compact would have failed).  pubkeys_out64 n*64: `secp256k1_pubkey` objects
+ * (pk_format 1 of the verification calls reads them), 64 zero bytes where results[i] == 0. */
+S2K_API int secp256k1_ecdsa_recover_batch(s2k_engine* e, int32_t* results, unsigned char* pubkeys_out64, const unsigned char* sigs64,
+                                          const unsigned char* recids, const unsigned char* msghash32, size_t n);
+S2K_API int secp256k1_ecdsa_recover_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* pubkeys_out64, const unsigned char* sigs64,
+                                              const unsigned char* recids, const unsigned char* msghash32, size_t n);
+
 /* ---- half-aggregated Schnorr signature verification ------------------------------------------------------------------
  * *result = secp256k1_schnorrsig_aggverify(ctx, pubkeys, msgs32, n, aggsig, aggsig_len)
  *                                       (include/secp256k1_schnorrsig_halfagg.h, src/modules/schnorrsig_halfagg/main_impl.h:108-198)
@@ -269,6 +296,12 @@ S2K_API int secp256k1_schnorrsig_verify_amd(const void* ctx, const unsigned char
 S2K_API int secp256k1_pedersen_verify_tally_amd(const void* ctx, const void* const* commits, size_t pcnt, const void* const* ncommits, size_t ncnt);
 S2K_API int secp256k1_surjectionproof_verify_amd(const void* ctx, const void* proof, const void* ephemeral_input_tags, size_t n_ephemeral_input_tags,
                                                  const void* ephemeral_output_tag);
+/*   secp256k1_ecdsa_verify(ctx, sig, msghash32, pubkey)                                include/secp256k1.h:622
+ *   secp256k1_ecdsa_recover(ctx, pubkey, sig, msghash32)                               include/secp256k1_recovery.h:112
+ * sig: the 64-byte secp256k1_ecdsa_signature object / the 65-byte secp256k1_ecdsa_recoverable_signature object (the limbs of
+ * r and s, then the recovery id); pubkey: the 64-byte secp256k1_pubkey object (written by the recovery form: zeroed on failure). */
+S2K_API int secp256k1_ecdsa_verify_amd(const void* ctx, const void* sig, const unsigned char* msghash32, const void* pubkey);
+S2K_API int secp256k1_ecdsa_recover_amd(const void* ctx, void* pubkey, const void* signature, const unsigned char* msghash32);
 
 /* ---- Pedersen commitment tallies ------------------------------------------------------------------------------------
  * results[t] = secp256k1_pedersen_verify_tally(ctx, pos_t, pcnt_t, neg_t, ncnt_t)
@@ -378,6 +411,8 @@ S2K_API int secp256k1_rangeproof_verify_batch_ptrs_group(s2k_group* g, int32_t* 
                                                          const unsigned char* const* extra, const size_t* elens, const void* const* gen_objs, size_t n);
 S2K_API int secp256k1_schnorrsig_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const unsigned char* msgs,
                                                     size_t msglen, const unsigned char* pubkeys, int pk_format, size_t n);
+S2K_API int secp256k1_ecdsa_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
+                                               const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format, size_t n);
 S2K_API int s2k_ecmult_multi_group(s2k_group* g, unsigned char* r_xy, int32_t* r_inf, const unsigned char* g_sc, const unsigned char* sc,
                                    const unsigned char* pt_xy, const unsigned char* pt_inf, size_t n);
 S2K_API int s2k_ecmult_multi_group_dev(s2k_group* g, unsigned char* r_xy, int32_t* r_inf, const unsigned char* g_sc_dev0,

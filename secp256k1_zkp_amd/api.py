@@ -47,6 +47,30 @@ def _dp(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+_ECDSA_PK_BYTES = {0: 33, 1: 64, 2: 65}     # compressed / secp256k1_pubkey object / uncompressed or hybrid
+
+
+def _ecdsa_args(what, sigs, msghashes, pubkeys, sig_format, pk_format):
+    """shape checks shared by Engine.ecdsa_verify_batch and Group.ecdsa_verify_batch; returns (sigs, sig_off or None, msghashes, pubkeys, n)"""
+    if sig_format not in (0, 1, 2) or pk_format not in _ECDSA_PK_BYTES:
+        raise ValueError(f"{what}: sig_format must be 0, 1 or 2 and pk_format 0, 1 or 2")
+    off = None
+    if sig_format == 2:
+        if isinstance(sigs, tuple) and len(sigs) == 2:
+            data, off = _u8(sigs[0]), np.ascontiguousarray(sigs[1], dtype=np.uint64)       # already packed: (data, offsets[n+1])
+        else:
+            data, off = Engine.pack([bytes(x) for x in sigs])
+        n = off.size - 1
+        _offsets_ok(what + " sigs", off, data.size)
+        sigs = data
+    else:
+        sigs = _u8(sigs); n = sigs.size // 64
+        _need(what + " sigs", sigs, 64 * n)
+    msghashes = _u8(msghashes); pubkeys = _u8(pubkeys)
+    _need(what + " msghashes", msghashes, 32 * n); _need(what + " pubkeys", pubkeys, _ECDSA_PK_BYTES[pk_format] * n)
+    return sigs, off, msghashes, pubkeys, n
+
+
 class Engine:
     """One engine per GPU/process (owns a stream, the generator table and an HBM workspace)."""
 
@@ -190,6 +214,38 @@ class Engine:
         n = sigs.numel() // 64
         self._check(self._lib.secp256k1_schnorrsig_verify_batch_dev(self._h, stream, _dp(results), _dp(sigs), _dp(msgs), msglen, _dp(pubkeys),
                                                                     pk_format, n), "secp256k1_schnorrsig_verify_batch_dev")
+
+    # ---- secp256k1_ecdsa_verify (secp256k1.c:498-512, ecdsa_impl.h:195-272) and secp256k1_ecdsa_recover (modules/recovery/main_impl.h:87-157), batched ----
+    def ecdsa_verify_batch(self, sigs, msghashes, pubkeys, sig_format=0, pk_format=0):
+        """sig_format 0: n*64 compact, 1: n*64 secp256k1_ecdsa_signature objects, 2: DER -- a list of bytes (packed here) or the tuple (data, offsets[n+1]);
+        pk_format 0: n*33 compressed, 1: n*64 secp256k1_pubkey objects, 2: n*65 uncompressed / hybrid"""
+        sigs, off, msghashes, pubkeys, n = _ecdsa_args("ecdsa_verify_batch", sigs, msghashes, pubkeys, sig_format, pk_format)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_ecdsa_verify_batch(self._h, _p(res), _p(sigs), _p(off), sig_format, _p(msghashes), _p(pubkeys), pk_format, n),
+                    "secp256k1_ecdsa_verify_batch")
+        return res
+
+    def ecdsa_verify_batch_dev(self, results, sigs, msghashes, pubkeys, sig_format=0, pk_format=0, sig_off=None, n=None, stream=None):
+        """every array in HBM (torch tensors; sig_off: int64 / uint64 offsets[n+1], DER only)"""
+        if sig_format == 2 and sig_off is None:
+            raise ValueError("ecdsa_verify_batch_dev: DER signatures need sig_off")
+        if n is None:
+            n = sig_off.numel() - 1 if sig_format == 2 else sigs.numel() // 64
+        self._check(self._lib.secp256k1_ecdsa_verify_batch_dev(self._h, stream, _dp(results), _dp(sigs), _dp(sig_off) if sig_format == 2 else None, sig_format,
+                                                               _dp(msghashes), _dp(pubkeys), pk_format, n), "secp256k1_ecdsa_verify_batch_dev")
+
+    def ecdsa_recover_batch(self, sigs64, recids, msghashes):
+        """-> (results[n], pubkeys64[n, 64]): secp256k1_pubkey objects (pk_format 1 of ecdsa_verify_batch), zero where results[i] == 0"""
+        sigs64 = _u8(sigs64); recids = _u8(recids); msghashes = _u8(msghashes); n = sigs64.size // 64
+        _need("ecdsa_recover_batch sigs64", sigs64, 64 * n); _need("ecdsa_recover_batch recids", recids, n); _need("ecdsa_recover_batch msghashes", msghashes, 32 * n)
+        res = np.zeros(n, np.int32); pk = np.zeros((n, 64), np.uint8)
+        self._check(self._lib.secp256k1_ecdsa_recover_batch(self._h, _p(res), _p(pk), _p(sigs64), _p(recids), _p(msghashes), n), "secp256k1_ecdsa_recover_batch")
+        return res, pk
+
+    def ecdsa_recover_batch_dev(self, results, pubkeys_out64, sigs64, recids, msghashes, n=None, stream=None):
+        n = sigs64.numel() // 64 if n is None else n
+        self._check(self._lib.secp256k1_ecdsa_recover_batch_dev(self._h, stream, _dp(results), _dp(pubkeys_out64), _dp(sigs64), _dp(recids), _dp(msghashes), n),
+                    "secp256k1_ecdsa_recover_batch_dev")
 
     def bppp_norm_product_verify_batch_dev(self, results, proofs, proof_len, transcripts, rho, gens33_dev, gens33_host, g_len, c_vec, c_vec_len, commits33, n,
                                            stream=None):
@@ -418,6 +474,13 @@ class Group:
         res = np.zeros(n, np.int32)
         self._check(self._lib.secp256k1_schnorrsig_verify_batch_group(self._h, _p(res), _p(sigs), _p(msgs), msglen, _p(pubkeys), pk_format, n),
                     "secp256k1_schnorrsig_verify_batch_group")
+        return res
+
+    def ecdsa_verify_batch(self, sigs, msghashes, pubkeys, sig_format=0, pk_format=0):
+        sigs, off, msghashes, pubkeys, n = _ecdsa_args("ecdsa_verify_batch_group", sigs, msghashes, pubkeys, sig_format, pk_format)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_ecdsa_verify_batch_group(self._h, _p(res), _p(sigs), _p(off), sig_format, _p(msghashes), _p(pubkeys), pk_format, n),
+                    "secp256k1_ecdsa_verify_batch_group")
         return res
 
     def ecmult_multi(self, sc, pt_xy, g_sc=None, pt_inf=None):

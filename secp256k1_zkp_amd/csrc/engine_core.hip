@@ -778,6 +778,34 @@ extern "C" int secp256k1_schnorrsig_verify_amd(const void* ctx, const unsigned c
     if (!secp256k1_schnorrsig_verify_batch(e, &res, sig64, msglen ? msg : &dummy, msglen, (const unsigned char*)pubkey, 1, 1)) return 0;
     return res;
 }
+// include/secp256k1.h:622 -- sig points at the 64-byte secp256k1_ecdsa_signature object, pubkey at the 64-byte secp256k1_pubkey object
+// (the kernels live in engine_ecdsa.hip)
+extern "C" int secp256k1_ecdsa_verify_amd(const void* ctx, const void* sig, const unsigned char* msghash32, const void* pubkey) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!sig || !msghash32 || !pubkey) return s2k_fail_arg("secp256k1_ecdsa_verify_amd", "illegal argument (ARG_CHECK)");
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0;
+    if (!secp256k1_ecdsa_verify_batch(e, &res, (const unsigned char*)sig, nullptr, 1, msghash32, (const unsigned char*)pubkey, 1, 1)) return 0;
+    return res;
+}
+// include/secp256k1_recovery.h:112 -- signature points at the 65-byte secp256k1_ecdsa_recoverable_signature object: the little-endian
+// limbs of r and s, then the recovery id (src/modules/recovery/main_impl.h:13-36); pubkey receives a secp256k1_pubkey object
+extern "C" int secp256k1_ecdsa_recover_amd(const void* ctx, void* pubkey, const void* signature, const unsigned char* msghash32) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!pubkey || !signature || !msghash32) return s2k_fail_arg("secp256k1_ecdsa_recover_amd", "illegal argument (ARG_CHECK)");
+    memset(pubkey, 0, 64);
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    const unsigned char* o = (const unsigned char*)signature;
+    unsigned char sig64[64];
+    for (int i = 0; i < 32; i++) { sig64[i] = o[31 - i]; sig64[32 + i] = o[63 - i]; }      // limbs -> compact big-endian
+    int32_t res = 0;
+    if (!secp256k1_ecdsa_recover_batch(e, &res, (unsigned char*)pubkey, sig64, o + 64, msghash32, 1)) { memset(pubkey, 0, 64); return 0; }
+    return res;
+}
 // include/secp256k1_generator.h:190 -- arrays of pointers to 64-byte secp256k1_pedersen_commitment objects
 extern "C" int secp256k1_pedersen_verify_tally_amd(const void* ctx, const void* const* commits, size_t pcnt, const void* const* ncommits, size_t ncnt) {
     (void)ctx;
@@ -1072,6 +1100,32 @@ extern "C" int secp256k1_schnorrsig_verify_batch_group(s2k_group* g, int32_t* re
         jobs[i] = [=]() -> int {
             if (hi == lo) return 1;
             return secp256k1_schnorrsig_verify_batch(e, results + lo, sigs + 64 * lo, msgs ? msgs + msglen * lo : nullptr, msglen, pubkeys + pkb * lo, pk_format, hi - lo);
+        };
+    }
+    const int ok = group_run(g, jobs);
+    if (!ok) memset(results, 0, sizeof(int32_t) * n);
+    return ok;
+}
+// (DER: every engine gets the whole packed array and its own window of the offsets; the host form uploads only the bytes that window spans)
+extern "C" int secp256k1_ecdsa_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
+                                                  const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format, size_t n) {
+    const char* who = "secp256k1_ecdsa_verify_batch_group";
+    if (!g || g->eng.empty()) return s2k_fail(who, "null group");
+    if (n == 0) return 1;
+    if (!results || !sigs || !msghash32 || !pubkeys || (sig_format == 2 && !sig_off)) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    if (sig_format < 0 || sig_format > 2 || pk_format < 0 || pk_format > 2) return s2k_fail_arg(who, "unknown sig_format / pk_format");
+    std::lock_guard<std::mutex> call(g->call_mu);
+    memset(results, 0, sizeof(int32_t) * n);
+    const size_t k = g->eng.size(), pkb = pk_format == 0 ? 33 : pk_format == 1 ? 64 : 65;
+    const int der = sig_format == 2;
+    std::vector<std::function<int()>> jobs(k);
+    for (size_t i = 0; i < k; i++) {
+        size_t lo, hi; group_share(n, k, i, lo, hi);
+        s2k_engine* e = g->eng[i];
+        jobs[i] = [=]() -> int {
+            if (hi == lo) return 1;
+            return secp256k1_ecdsa_verify_batch(e, results + lo, der ? sigs : sigs + 64 * lo, der ? sig_off + lo : nullptr, sig_format, msghash32 + 32 * lo,
+                                                pubkeys + pkb * lo, pk_format, hi - lo);
         };
     }
     const int ok = group_run(g, jobs);
