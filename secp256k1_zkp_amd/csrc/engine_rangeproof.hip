@@ -55,8 +55,19 @@ __global__ void __launch_bounds__(64)
 k_rp_sum(rp_ws ws, u32 gen_valid, size_t n) {
     const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     u32 cF = 0, cG = 0, rings = 0;
+    // the last ring key, brought to affine with one inversion for the wavefront (the workgroup): lanes without a finite key hand in Z = 1;
+    // a Z that is 0 mod p somewhere (no finite point has one) sends every lane through its own exact inversion
+    const int active = p < n && ws.rec[p < n ? p : 0].ok;
+    gej last; int sum_ok = 1, finite = 0;
+    fe z; fe_set_int(z, 1);
+    if (active) {
+        finite = rp_sum_key(last, sum_ok, ws.rec[p], ws.pub0 + p * RP_MAX_RINGS * RP_GEJ_WORDS, ws.lift_ok + p * RP_MAX_RINGS);
+        if (finite) z = last.z;
+    }
+    fe zi;
+    if (!fe_inv_lanes(zi, z)) fe_inv(zi, z);
+    if (active) rp_sum_store(ws.rec[p], ws.pub0 + p * RP_MAX_RINGS * RP_GEJ_WORDS, last, sum_ok, zi);
     if (p < n) {
-        rp_sum(ws.rec[p], ws.pub0 + p * RP_MAX_RINGS * RP_GEJ_WORDS, ws.lift_ok + p * RP_MAX_RINGS);
         const rp_rec& rec = ws.rec[p];
         if (rec.ok) {
             rings = rec.rings;

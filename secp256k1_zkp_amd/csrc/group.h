@@ -173,12 +173,17 @@ S2K_HD void gej_add_var(gej& r, const gej& a, const gej& b) {
 
 // Jacobian -> affine: one inversion + 1S + 3M (cf. secp256k1_ge_set_gej_var :177-196).  Output normalised.
 // Caller must handle a.inf.
-S2K_HD void ge_set_gej(ge& r, const gej& a) {
-    fe zi, zi2, zi3;
-    fe_inv(zi, a.z);
+// ... with zi = 1/a.z from elsewhere (waveinv.h: one inversion for the wavefront)
+S2K_HD void ge_set_gej_zinv(ge& r, const gej& a, const fe& zi) {
+    fe zi2, zi3;
     fe_sqr(zi2, zi); fe_mul(zi3, zi2, zi);
     fe_mul(r.x, a.x, zi2); fe_mul(r.y, a.y, zi3);
     fe_normalize(r.x); fe_normalize(r.y);
+}
+S2K_HD void ge_set_gej(ge& r, const gej& a) {
+    fe zi;
+    fe_inv(zi, a.z);
+    ge_set_gej_zinv(r, a, zi);
 }
 
 // y^2 = x^3 + 7

@@ -129,6 +129,42 @@ S2K_HD void ds_add_multiple(ds_int& r, int32_t c, const ds_modulus md) {
     r.w[DS_LIMBS - 1] = (int32_t)(acc + r.w[DS_LIMBS - 1] + (int64_t)c * md.w[DS_LIMBS - 1]);
 }
 
+// The end of an inversion: g = 0, f = +-gcd = +-1 (or f = +-m when the input was 0, with d = 0), and d * input == f (mod m), |d| < 21 m.
+// f's top limb carries f's sign; d may come in any limb form ds_add_multiple takes.  o <- the inverse in [0, m) as 8 words.
+S2K_HD void ds_finish_words(u32 o[8], const ds_int& f, ds_int& d, const ds_modulus md) {
+    // r = d + 32 m > 0; quotient estimate q = r >> 256 (m = 2^256 - c, c < 2^129, so r - q m = (r mod 2^256) + q c < 2 m)
+    ds_add_multiple(d, 32, md);
+    const int32_t qest = d.w[DS_LIMBS - 1] >> 16;
+    ds_add_multiple(d, -qest, md);
+    { ds_int s = d; ds_add_multiple(s, -1, md); const int keep = s.w[DS_LIMBS - 1] >= 0;                 // one conditional subtraction
+#pragma unroll
+      for (int i = 0; i < DS_LIMBS; i++) d.w[i] = keep ? s.w[i] : d.w[i]; }
+    // sign of f: a negative f means the inverse is -d = m - d (for d != 0)
+    { const int fneg = f.w[DS_LIMBS - 1] < 0;
+      int32_t nz = 0;
+#pragma unroll
+      for (int i = 0; i < DS_LIMBS; i++) nz |= d.w[i];
+      ds_int s;
+#pragma unroll
+      for (int i = 0; i < DS_LIMBS; i++) s.w[i] = -d.w[i];
+      // -d + m, limbs renormalised
+      int64_t acc = 0;
+#pragma unroll
+      for (int i = 0; i < DS_LIMBS - 1; i++) { acc += (int64_t)s.w[i] + md.w[i]; s.w[i] = (int32_t)acc & DS_MASK; acc >>= DS_BITS; }
+      s.w[DS_LIMBS - 1] = (int32_t)(acc + s.w[DS_LIMBS - 1] + md.w[DS_LIMBS - 1]);
+      const int take = fneg & (nz != 0);
+#pragma unroll
+      for (int i = 0; i < DS_LIMBS; i++) d.w[i] = take ? s.w[i] : d.w[i]; }
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const int bit = 32 * j, i = bit / DS_BITS, sh = bit % DS_BITS;
+        u64 v = (u64)(u32)d.w[i] >> sh;
+        if (i + 1 < DS_LIMBS) v |= (u64)(u32)d.w[i + 1] << (DS_BITS - sh);
+        if (i + 2 < DS_LIMBS) v |= (u64)(u32)d.w[i + 2] << (2 * DS_BITS - sh);
+        o[j] = (u32)v;
+    }
+}
+
 // w (8 little-endian 32-bit words, value < m) -> w^-1 mod m (0 for 0).
 // UNIFORM = true: w is the same in every lane of the wavefront (waveinv.h).  The batch kernel then takes the low words of f and g
 // through v_readfirstlane and runs on the scalar unit (ds_batch_uniform); so, as the compiler sees that everything else is uniform
@@ -163,36 +199,98 @@ S2K_HD void ds_inverse_words(u32 o[8], const u32 w[8], const ds_modulus md) {
             if (DS_WAVE_ALL(gz == 0)) break;
         }
     }
-    // now g = 0, f = +-gcd = +-1 (or f = +-m when the input was 0, with d = 0), and d * input == f (mod m), |d| < 21 m.
-    // r = d + 32 m > 0; quotient estimate q = r >> 256 (m = 2^256 - c, c < 2^129, so r - q m = (r mod 2^256) + q c < 2 m)
-    ds_add_multiple(d, 32, md);
-    const int32_t qest = d.w[DS_LIMBS - 1] >> 16;
-    ds_add_multiple(d, -qest, md);
-    { ds_int s = d; ds_add_multiple(s, -1, md); const int keep = s.w[DS_LIMBS - 1] >= 0;                 // one conditional subtraction
-#pragma unroll
-      for (int i = 0; i < DS_LIMBS; i++) d.w[i] = keep ? s.w[i] : d.w[i]; }
-    // sign of f: a negative f means the inverse is -d = m - d (for d != 0)
-    { const int fneg = f.w[DS_LIMBS - 1] < 0;
-      int32_t nz = 0;
-#pragma unroll
-      for (int i = 0; i < DS_LIMBS; i++) nz |= d.w[i];
-      ds_int s;
-#pragma unroll
-      for (int i = 0; i < DS_LIMBS; i++) s.w[i] = -d.w[i];
-      // -d + m, limbs renormalised
-      int64_t acc = 0;
-#pragma unroll
-      for (int i = 0; i < DS_LIMBS - 1; i++) { acc += (int64_t)s.w[i] + md.w[i]; s.w[i] = (int32_t)acc & DS_MASK; acc >>= DS_BITS; }
-      s.w[DS_LIMBS - 1] = (int32_t)(acc + s.w[DS_LIMBS - 1] + md.w[DS_LIMBS - 1]);
-      const int take = fneg & (nz != 0);
-#pragma unroll
-      for (int i = 0; i < DS_LIMBS; i++) d.w[i] = take ? s.w[i] : d.w[i]; }
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        const int bit = 32 * j, i = bit / DS_BITS, sh = bit % DS_BITS;
-        u64 v = (u64)(u32)d.w[i] >> sh;
-        if (i + 1 < DS_LIMBS) v |= (u64)(u32)d.w[i + 1] << (DS_BITS - sh);
-        if (i + 2 < DS_LIMBS) v |= (u64)(u32)d.w[i + 2] << (2 * DS_BITS - sh);
-        o[j] = (u32)v;
-    }
+    ds_finish_words(o, f, d, md);
 }
+
+#if defined(__HIPCC__)
+// ---- the uniform inverse with its state across the lanes (device only) ----------------------------------------------------------------
+// ds_inverse_words<true> keeps f, g, d, e in scalar registers and walks their limbs one after the other: ~650 dependent scalar
+// instructions per batch for the two matrix applications.  Here lane i (0..8) of the wavefront holds limb i of each of the four
+// numbers, lanes 9..63 hold zeros and ride along, and a matrix application is three (d, e) or two (f, g) v_mad_i64_i32 per number in
+// all lanes at once.  The batch kernel stays on the scalar unit (ds_batch_uniform on lane 0's f and g, v_readlane); so does the
+// choice of ka, kb, from lane 0's d and e, as in ds_apply<true>.
+//
+// Carries.  Lane i forms S_i = t00 a_i + t01 b_i (+ ka m_i); the new number is (sum S_i 2^(30 i)) / 2^30, and S_0 = 0 mod 2^30.  S_i is
+// cut into lo = S_i mod 2^30, mid = (S_i >> 30) mod 2^30 and top = S_i >> 60, and
+//      u_j  = lo(S_(j+1)) + mid(S_j)                      in [0, 2^31 - 2]              (lo comes down one lane: the division by 2^30)
+//      a'_j = (u_j mod 2^30) + (u_(j-1) >> 30) + top(S_(j-1))                            (the carry goes up one lane)
+// Lane 8 keeps its whole signed S_8 >> 30 (no mask, no carry out), so lanes 9.. stay 0.  That is one and a half carry passes and two DPP
+// moves per number.  Bound: |t00| + |t01| <= 2^30 for a matrix of 30 division steps, |m_i| < 2^30, 0 <= ka < 2^30, so with limbs
+// |a_i| <= 2^30 + 3 going in, |S_i| <= 2^30 (2^30 + 3) + 2^30 (2^30 - 1) = 2^61 + 2^31: top is in [-3, 2], the carry in [-3, 3], and
+//      limbs 0..7 come out in [-3, 2^30 + 2], limb 0 in [0, 2^30) exactly (nothing is carried into it),
+// which is the bound going in again (the moduli's own limbs, the state of f before the first batch, are below 2^30 in size).  The
+// limbs between batches are therefore redundant: a number is the sum of its limbs, not their concatenation, and the sign of the top
+// limb is the number's only after the carry pass that the final reduction starts with.  The VALUES of f, g, d, e after every batch
+// are those of ds_inverse_words<true> (ka depends only on d, e mod 2^30), so |d|, |e| < 21 m as in the header of this file, the top
+// limb stays below 2^22 in size, and the result is bit for bit the same.  tests/test_cpu_wave_inverse_lanes.py runs a model of this
+// scheme with explicit 64-bit wraparound and asserts the ranges; that test guards the bound.
+//
+// All 64 lanes must be active and call it in lock step with the same w.  The lane index is threadIdx.x & 63 (as wi_lane, waveinv.h):
+// one-dimensional workgroups.
+S2K_D int32_t dsl_from_below(int32_t x) { return __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, true); }     // row_shr:1: lane i <- lane i - 1, 0 into lane 0
+S2K_D int32_t dsl_from_above(int32_t x) { return __builtin_amdgcn_update_dpp(0, x, 0x101, 0xf, 0xf, true); }     // row_shl:1: lane i <- lane i + 1
+// column sums -> limbs.  lm: 2^30 - 1 in lanes 0..7, all ones above; cm: all ones in lanes 0..7, 0 above.
+S2K_D int32_t dsl_carry(int64_t s, int32_t lm, int32_t cm) {
+    const int32_t lo = (int32_t)s & DS_MASK, mid = (int32_t)(s >> DS_BITS) & lm, top = (int32_t)(s >> (2 * DS_BITS));
+    const int32_t u = dsl_from_above(lo) + mid;
+    const int32_t c = ((u >> DS_BITS) + top) & cm;
+    return (u & lm) + dsl_from_below(c);
+}
+S2K_D void dsl_gather(ds_int& r, int32_t v) {
+#pragma unroll
+    for (int i = 0; i < DS_LIMBS; i++) r.w[i] = __builtin_amdgcn_readlane(v, i);
+}
+
+// dump (DUMP only): after batch `it`, lanes 0..8 write limb `lane` of f, g, d, e to dump[(4 it + {0, 1, 2, 3}) 9 + lane]; *batches gets
+// the number of batches run.  For tests/wave_inverse.
+template <bool DUMP = false>
+S2K_D void ds_inverse_words_lanes(u32 o[8], const u32 w[8], const ds_modulus md, int32_t* dump = nullptr, int* batches = nullptr) {
+    const u32 lane = (u32)(threadIdx.x & 63u);
+    const int32_t lm = lane < DS_LIMBS - 1 ? DS_MASK : -1, cm = lane < DS_LIMBS - 1 ? -1 : 0;
+    int32_t m = 0, f, g = 0, d = 0, e = lane == 0 ? 1 : 0;
+#pragma unroll
+    for (int i = 0; i < DS_LIMBS; i++) {
+        const int bit = DS_BITS * i, idx = bit >> 5, sh = bit & 31;
+        u64 v = w[idx];
+        if (idx + 1 < 8) v |= (u64)w[idx + 1] << 32;
+        g = lane == (u32)i ? (int32_t)((u32)(v >> sh) & (u32)DS_MASK) : g;
+        if (md.w[i] != 0) m = lane == (u32)i ? md.w[i] : m;
+    }
+    f = m;
+    int32_t zeta = -1;
+    int it = 0;
+#pragma unroll 1
+    for (; it < DS_BATCHES; it++) {
+        int32_t t[4];
+        zeta = ds_batch_uniform(DS_UNIFORM(zeta), (u32)__builtin_amdgcn_readlane(f, 0), (u32)__builtin_amdgcn_readlane(g, 0), t);
+        const u32 d0 = (u32)__builtin_amdgcn_readlane(d, 0), e0 = (u32)__builtin_amdgcn_readlane(e, 0);
+        const int32_t ka = (int32_t)((0u - ((u32)t[0] * d0 + (u32)t[1] * e0) * md.inv) & (u32)DS_MASK);      // ka * m == -(t00 d + t01 e)  (mod 2^30)
+        const int32_t kb = (int32_t)((0u - ((u32)t[2] * d0 + (u32)t[3] * e0) * md.inv) & (u32)DS_MASK);
+        const int64_t sd = (int64_t)t[0] * d + (int64_t)t[1] * e + (int64_t)ka * m, se = (int64_t)t[2] * d + (int64_t)t[3] * e + (int64_t)kb * m;
+        const int64_t sf = (int64_t)t[0] * f + (int64_t)t[1] * g, sg = (int64_t)t[2] * f + (int64_t)t[3] * g;
+        d = dsl_carry(sd, lm, cm); e = dsl_carry(se, lm, cm);
+        f = dsl_carry(sf, lm, cm); g = dsl_carry(sg, lm, cm);
+        if (DUMP) {
+            if (lane < DS_LIMBS) {
+                int32_t* p = dump + (size_t)4 * DS_LIMBS * it + lane;
+                p[0] = f; p[DS_LIMBS] = g; p[2 * DS_LIMBS] = d; p[3 * DS_LIMBS] = e;
+            }
+        }
+        // as in ds_inverse_words: once g = 0 further batches change nothing.  A g that is 0 mostly arrives in redundant form (a limb of
+        // 2^30 under limbs of 2^30 - 1 and one of -1, moving up a lane per batch), so the test is made on a copy with its carries
+        // rippled all the way: 8 steps of one lane each bring limbs 0..7 to [0, 2^30), and then every limb 0 is g = 0.
+        if (it >= DS_BATCHES - 5) {
+            int32_t z = g;
+#pragma unroll
+            for (int k = 0; k < DS_LIMBS - 1; k++) z = (z & lm) + dsl_from_below((z >> DS_BITS) & cm);
+            if (__all(z == 0)) { it++; break; }
+        }
+    }
+    if (DUMP) *batches = it;
+    // the limbs back into every lane (uniform: the rest is scalar code, once per inversion), f brought to canonical limbs for its sign
+    ds_int fw, dw;
+    dsl_gather(fw, f); dsl_gather(dw, d);
+    ds_add_multiple(fw, 0, md);
+    ds_finish_words(o, fw, dw, md);
+}
+#endif

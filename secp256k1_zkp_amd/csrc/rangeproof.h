@@ -250,10 +250,11 @@ S2K_HD void rp_lift(const rp_rec& rec, u32* pub0_ring, unsigned char* lift_ok, c
 }
 
 // ---- K2: key of the last ring (rangeproof_impl.h:619-631) ------------------------------------------------------
-S2K_HD void rp_sum(rp_rec& rec, u32* pub0 /*[32][28]*/, const unsigned char* lift_ok /*[32]*/) {
-    if (!rec.ok) return;
+// In two halves, so that the device can take the to-affine inversion between them once per wavefront (k_rp_sum: fe_inv_lanes):
+// rp_sum_key -> the last key in Jacobian form, `ok`, and whether it is finite (then it needs 1/Z); rp_sum_store with zi = 1/last.z.
+S2K_HD int rp_sum_key(gej& last, int& ok, const rp_rec& rec, const u32* pub0 /*[32][28]*/, const unsigned char* lift_ok /*[32]*/) {
     gej acc; gej_load28_h(acc, rec.accj);
-    int ok = 1;
+    ok = 1;
     for (u32 i = 0; i + 1 < rec.rings; i++) {
         ok &= lift_ok[i];
         gej c; gej_load28_h(c, pub0 + RP_GEJ_WORDS * i);
@@ -266,12 +267,22 @@ S2K_HD void rp_sum(rp_rec& rec, u32* pub0 /*[32][28]*/, const unsigned char* lif
     fe_norm_weak(acc.x);
     ge cm;
     for (int i = 0; i < 9; i++) { cm.x.n[i] = rec.commit[i]; cm.y.n[i] = rec.commit[9 + i]; }
-    gej last; const int f = gej_add_ge(last, acc, cm);
+    const int f = gej_add_ge(last, acc, cm);
     if (f == GEJ_ADD_NEEDS_DOUBLE) { gej t; gej_double(t, last); last = t; }
     if (last.inf) ok = 0;
-    else { ge a; ge_set_gej(a, last); gej_set_ge(last, a); }          // every ring key leaves this stage with Z = 1 (rp_ring_shared relies on it)
+    return !last.inf;
+}
+S2K_HD void rp_sum_store(rp_rec& rec, u32* pub0, gej& last, int ok, const fe& zi) {
+    if (!last.inf) { ge a; ge_set_gej_zinv(a, last, zi); gej_set_ge(last, a); }   // every ring key leaves this stage with Z = 1 (rp_ring_shared relies on it)
     gej_store28_h(pub0 + RP_GEJ_WORDS * (rec.rings - 1), last);
     if (!ok) rec.ok = 0;
+}
+S2K_HD void rp_sum(rp_rec& rec, u32* pub0 /*[32][28]*/, const unsigned char* lift_ok /*[32]*/) {
+    if (!rec.ok) return;
+    gej last; int ok;
+    fe zi; fe_set_zero(zi);
+    if (rp_sum_key(last, ok, rec, pub0, lift_ok)) fe_inv(zi, last.z);
+    rp_sum_store(rec, pub0, last, ok, zi);
 }
 
 // ---- K3: one ring (borromean_impl.h:70-98) ------------------------------------------------------------------------

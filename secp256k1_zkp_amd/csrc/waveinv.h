@@ -7,8 +7,10 @@
 //     the 9 limbs of a neighbour come through ds_bpermute, which takes no VALU slot): lane l holds z_0 .. z_l and z_l .. z_63;
 //   * P = z_0 .. z_63 is inverted ONCE.  Its value is the same in every lane, so the 30-step batch kernel of modinv.h, which only looks
 //     at the low words of f and g, takes them through v_readfirstlane and compiles to s_* arithmetic with no wave vote
-//     (ds_batch_uniform): it runs on the scalar unit, idle in this kernel, while the sibling wave keeps the VALU.  The compiler sees the
-//     whole state uniform and puts the matrix application (ds_apply) on the scalar unit too: ~19 000 scalar instructions per inversion;
+//     (ds_batch_uniform): it runs on the scalar unit, idle in this kernel, while the sibling wave keeps the VALU.  The four numbers of
+//     the inversion lie across the lanes, one limb each, and the matrix application is a few v_mad_i64_i32 and DPP moves per batch
+//     (ds_inverse_words_lanes, modinv.h; -DS2K_WAVEINV_SCALAR_APPLY selects the earlier form, ds_apply on the scalar unit too:
+//     ~19 000 dependent scalar instructions per inversion);
 //   * 1/z_l = P^-1 . (z_0 .. z_(l-1)) . (z_(l+1) .. z_63).
 // Values are exactly those of fe_inv (the inverse is unique).  If any lane's z is 0 mod p, P is 0 and every lane gets 0 back as the
 // return value (the outputs are then meaningless).  Magnitude contract: z <= 2, as fe_inv; outputs have magnitude 1.
@@ -24,6 +26,12 @@ S2K_D void wi_fetch(fe& r, const fe& a, u32 src) {              // r = lane src'
 #pragma unroll
     for (int i = 0; i < FE_LIMBS; i++) r.n[i] = (u32)__builtin_amdgcn_ds_bpermute(addr, (int)a.n[i]);
 }
+#if defined(S2K_WAVEINV_SCALAR_APPLY)          /* the form before the lane-distributed one as the default: A/B libraries */
+#define WI_SCALAR_APPLY true
+#else
+#define WI_SCALAR_APPLY false
+#endif
+template <bool SCALAR_APPLY = WI_SCALAR_APPLY>
 S2K_D int fe_inv_wave(fe& r, const fe& z) {
     const u32 l = wi_lane();
     fe pre = z, suf = z;
@@ -46,7 +54,8 @@ S2K_D int fe_inv_wave(fe& r, const fe& z) {
     fe_normalize(P);
     const int ok = !fe_is_zero_normalized(P);
     u32 w[8], o[8]; fe_to_words(w, P);
-    ds_inverse_words<true>(o, w, DS_MOD_P);
+    if (SCALAR_APPLY) ds_inverse_words<true>(o, w, DS_MOD_P);
+    else ds_inverse_words_lanes(o, w, DS_MOD_P);
     fe ip; fe_from_words(ip, o);
     fe_mul(r, ip, q);
     return ok;

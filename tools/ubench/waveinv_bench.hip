@@ -1,7 +1,9 @@
 // Micro-benchmark: what one to-affine inversion costs a VALU-bound kernel -- per-lane fe_inv (modinv.h) against the wave-batched
-// fe_inv_wave (waveinv.h), whose division-step control runs on the scalar unit.
+// fe_inv_wave (waveinv.h), whose division-step control runs on the scalar unit, in its two forms.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../secp256k1_zkp_amd/csrc -o waveinv_bench waveinv_bench.hip
 //   ./waveinv_bench [iters] [VALU per fe_mul pair] [F]
+// Three forms in one run: per-lane fe_inv, fe_inv_wave with the matrix application on the scalar unit (fe_inv_wave<true>, the earlier
+// form), and fe_inv_wave with it across the lanes (fe_inv_wave<false>, modinv.h: ds_inverse_words_lanes).
 // Every wavefront runs `iters` rounds of { F dependent fe_mul pairs (the VALU-bound filler: point arithmetic) ; one inversion }, at
 // exactly 2 waves per SIMD (256-lane workgroups holding 80 KiB of LDS each: two per CU), the occupancy of k_rp_rings_shared.  The waves
 // drift apart, so one wave's inversion runs beside the other's filler as in the kernel.  The cost of an inversion is the time it adds
@@ -19,7 +21,7 @@
 
 extern __shared__ unsigned char dyn_lds[];
 
-template <int MODE>                             // 0: filler only, 1: + fe_inv per lane, 2: + fe_inv_wave
+template <int MODE>                             // 0: filler only, 1: + fe_inv per lane, 2: + fe_inv_wave, scalar apply, 3: + fe_inv_wave, lanes
 __global__ void __launch_bounds__(256, 2) k_round(u32* out, u32 seed, int iters, int filler) {
     if (seed == 0xdeadbeefu) dyn_lds[threadIdx.x] = 1;
     fe a, b, c, d;
@@ -36,7 +38,8 @@ __global__ void __launch_bounds__(256, 2) k_round(u32* out, u32 seed, int iters,
 #pragma unroll 1
         for (int k = 0; k < filler; k++) fe_mul2(a, a, b, c, c, d);
         if (MODE == 1) { fe r; fe_inv(r, a); b = r; }
-        if (MODE == 2) { fe r; okall &= fe_inv_wave(r, a); b = r; }
+        if (MODE == 2) { fe r; okall &= fe_inv_wave<true>(r, a); b = r; }
+        if (MODE == 3) { fe r; okall &= fe_inv_wave<false>(r, a); b = r; }
     }
     u32 x = (u32)okall;
 #pragma unroll
@@ -70,12 +73,13 @@ int main(int argc, char** argv) {
     const double filler_valu = argc > 2 ? atof(argv[2]) : 0.0;     // VALU per fe_mul pair (from the static count), 0: report fe_mul-pair units
     const int filler = argc > 3 ? atoi(argv[3]) : 24;
     u32* out; CHECK(hipMalloc(&out, (size_t)blocks * 256 * sizeof(u32)));
-    const double t0 = run<0>(blocks, iters, filler, out), t1 = run<1>(blocks, iters, filler, out), t2 = run<2>(blocks, iters, filler, out);
-    const double c1 = (t1 - t0) / t0 * filler, c2 = (t2 - t0) / t0 * filler;       // in fe_mul pairs of the filler
-    printf("{\"cus\": %d, \"blocks\": %d, \"iters\": %d, \"filler_pairs\": %d, \"ms_filler\": %.4f, \"ms_fe_inv\": %.4f, \"ms_fe_inv_wave\": %.4f,\n",
-           prop.multiProcessorCount, blocks, iters, filler, t0, t1, t2);
-    printf(" \"cost_fe_inv_pairs\": %.2f, \"cost_fe_inv_wave_pairs\": %.2f, \"wave_over_lane\": %.4f", c1, c2, c2 / c1);
-    if (filler_valu > 0) printf(", \"cost_fe_inv_valu_eq\": %.0f, \"cost_fe_inv_wave_valu_eq\": %.0f", c1 * filler_valu, c2 * filler_valu);
+    const double t0 = run<0>(blocks, iters, filler, out), t1 = run<1>(blocks, iters, filler, out), t2 = run<2>(blocks, iters, filler, out), t3 = run<3>(blocks, iters, filler, out);
+    const double c1 = (t1 - t0) / t0 * filler, c2 = (t2 - t0) / t0 * filler, c3 = (t3 - t0) / t0 * filler;       // in fe_mul pairs of the filler
+    printf("{\"cus\": %d, \"blocks\": %d, \"iters\": %d, \"filler_pairs\": %d, \"ms_filler\": %.4f, \"ms_fe_inv\": %.4f, \"ms_fe_inv_wave_scalar\": %.4f, \"ms_fe_inv_wave_lanes\": %.4f,\n",
+           prop.multiProcessorCount, blocks, iters, filler, t0, t1, t2, t3);
+    printf(" \"cost_fe_inv_pairs\": %.2f, \"cost_wave_scalar_pairs\": %.2f, \"cost_wave_lanes_pairs\": %.2f, \"wave_scalar_over_lane\": %.4f, \"wave_lanes_over_lane\": %.4f",
+           c1, c2, c3, c2 / c1, c3 / c1);
+    if (filler_valu > 0) printf(", \"cost_fe_inv_valu_eq\": %.0f, \"cost_wave_scalar_valu_eq\": %.0f, \"cost_wave_lanes_valu_eq\": %.0f", c1 * filler_valu, c2 * filler_valu, c3 * filler_valu);
     printf("}\n");
     CHECK(hipFree(out));
     return 0;
