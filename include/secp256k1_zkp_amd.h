@@ -213,6 +213,28 @@ S2K_API int secp256k1_ecdsa_recover_batch(s2k_engine* e, int32_t* results, unsig
 S2K_API int secp256k1_ecdsa_recover_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* pubkeys_out64, const unsigned char* sigs64,
                                               const unsigned char* recids, const unsigned char* msghash32, size_t n);
 
+/* ---- Whitelist-signature batch verification -------------------------------------------------------------------------
+ * results[i] = secp256k1_whitelist_signature_parse(ctx, &sig, sigs + sig_off[i], sig_off[i+1] - sig_off[i]) &&
+ *              secp256k1_whitelist_verify(ctx, &sig, online keys of list L, offline keys of list L, length of list L, sub64 + 64 i),   L = list_of[i]
+ *                                       (include/secp256k1_whitelist.h, src/modules/whitelist/main_impl.h:99-151)
+ * sigs: serialised signatures back to back (n_keys byte | e0 | s_0 .. s_{n_keys-1}), item i = sigs[sig_off[i] .. sig_off[i+1]).
+ * online64 / offline64: the key lists back to back, 64-byte `secp256k1_pubkey` opaque objects; list l owns keys
+ * [list_off[l], list_off[l+1]); list_off has n_lists + 1 non-decreasing entries starting at 0.  list_of[i] names item i's list;
+ * NULL means n_lists == n and item i uses list i.  A whitelist shared by the whole batch is therefore uploaded once.
+ * sub64 n*64: one `secp256k1_pubkey` object per item.
+ * An item whose list is longer than 255 keys, or whose signature is not 1 + 32 (list length + 1) bytes long, gets verdict 0 (not a
+ * call error) and costs no key work.  An all-zero key object, where the reference calls its illegal-argument callback and then
+ * reads an unset point, gives the item 0.  list_of[i] >= n_lists, decreasing offsets and NULL where the reference has ARG_CHECK
+ * are S2K_STATUS_ILLEGAL_ARGUMENT (return 0, results zeroed).
+ * _dev: the byte arrays and results are in HBM; the three offset / index arrays are HOST arrays, read before the call returns (as
+ * offsets_host of s2k_ecmult_multi_many_dev): the call plans its launches from them.  results is zeroed on the stream first. */
+S2K_API int secp256k1_whitelist_verify_batch(s2k_engine* e, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off,
+                                             const unsigned char* online64, const unsigned char* offline64, const uint64_t* list_off, size_t n_lists,
+                                             const uint32_t* list_of, const unsigned char* sub64, size_t n);
+S2K_API int secp256k1_whitelist_verify_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off_host,
+                                                 const unsigned char* online64, const unsigned char* offline64, const uint64_t* list_off_host, size_t n_lists,
+                                                 const uint32_t* list_of_host, const unsigned char* sub64, size_t n);
+
 /* ---- half-aggregated Schnorr signature verification ------------------------------------------------------------------
  * *result = secp256k1_schnorrsig_aggverify(ctx, pubkeys, msgs32, n, aggsig, aggsig_len)
  *                                       (include/secp256k1_schnorrsig_halfagg.h, src/modules/schnorrsig_halfagg/main_impl.h:108-198)
@@ -302,6 +324,11 @@ S2K_API int secp256k1_surjectionproof_verify_amd(const void* ctx, const void* pr
  * r and s, then the recovery id); pubkey: the 64-byte secp256k1_pubkey object (written by the recovery form: zeroed on failure). */
 S2K_API int secp256k1_ecdsa_verify_amd(const void* ctx, const void* sig, const unsigned char* msghash32, const void* pubkey);
 S2K_API int secp256k1_ecdsa_recover_amd(const void* ctx, void* pubkey, const void* signature, const unsigned char* msghash32);
+/*   secp256k1_whitelist_verify(ctx, sig, online_pubkeys, offline_pubkeys, n_keys, sub_pubkey)      include/secp256k1_whitelist.h
+ * sig: the secp256k1_whitelist_signature object {size_t n_keys; unsigned char data[32 * 256]}; the key arrays: n_keys 64-byte
+ * secp256k1_pubkey objects each (they may be NULL when n_keys is 0 here; the reference's ARG_CHECK refuses that). */
+S2K_API int secp256k1_whitelist_verify_amd(const void* ctx, const void* sig, const void* online_pubkeys, const void* offline_pubkeys, size_t n_keys,
+                                           const void* sub_pubkey);
 
 /* ---- Pedersen commitment tallies ------------------------------------------------------------------------------------
  * results[t] = secp256k1_pedersen_verify_tally(ctx, pos_t, pcnt_t, neg_t, ncnt_t)

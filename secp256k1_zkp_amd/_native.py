@@ -46,6 +46,8 @@ SIGNATURES = {
     "secp256k1_ecdsa_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_recover_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "secp256k1_ecdsa_recover_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_whitelist_verify_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),
+    "secp256k1_whitelist_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),
     "secp256k1_schnorrsig_aggverify_amd": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _sz, _vp, _sz]),
     "secp256k1_pedersen_verify_tally_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "secp256k1_rangeproof_verify_batch": (_c.c_int, [_vp] + [_vp] * 9 + [_sz]),
@@ -59,6 +61,7 @@ SIGNATURES = {
     "secp256k1_schnorrsig_verify_amd": (_c.c_int, [_vp, _vp, _vp, _sz, _vp]),
     "secp256k1_ecdsa_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "secp256k1_ecdsa_recover_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
+    "secp256k1_whitelist_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _vp]),
     "secp256k1_pedersen_verify_tally_amd": (_c.c_int, [_vp, _vp, _sz, _vp, _sz]),
     "secp256k1_surjectionproof_verify_amd": (_c.c_int, [_vp, _vp, _vp, _sz, _vp]),
     "secp256k1_surjectionproof_verify_batch": (_c.c_int, [_vp] + [_vp] * 6 + [_sz]),

@@ -247,6 +247,63 @@ class Engine:
         self._check(self._lib.secp256k1_ecdsa_recover_batch_dev(self._h, stream, _dp(results), _dp(pubkeys_out64), _dp(sigs64), _dp(recids), _dp(msghashes), n),
                     "secp256k1_ecdsa_recover_batch_dev")
 
+    # ---- secp256k1_whitelist_signature_parse + secp256k1_whitelist_verify (modules/whitelist/main_impl.h:99-151), batched ----
+    @staticmethod
+    def _whitelist_lists(what, lists_online, lists_offline, list_off, list_of, n):
+        """the key lists as the C call wants them: (online, offline, list_off[n_lists+1], n_lists, list_of or None)"""
+        if list_off is None:                                          # a list of per-list byte strings
+            online, list_off = Engine.pack([bytes(_u8(x)) for x in lists_online])
+            offline, off2 = Engine.pack([bytes(_u8(x)) for x in lists_offline])
+            if not np.array_equal(list_off, off2) or (list_off % 64).any():
+                raise ValueError(f"{what}: online and offline lists must have the same lengths, 64 bytes per key")
+            list_off = list_off // np.uint64(64)
+        else:                                                         # already packed: keys back to back, list_off in keys
+            online, offline = _u8(lists_online), _u8(lists_offline)
+            list_off = np.ascontiguousarray(list_off, dtype=np.uint64)
+            if list_off.size == 0:
+                raise ValueError(f"{what}: list_off needs n_lists + 1 entries")
+        n_lists = list_off.size - 1
+        keys = int(list_off.max())
+        if online.size < 64 * keys or offline.size < 64 * keys:
+            raise ValueError(f"{what}: the key arrays are shorter than list_off says")
+        if list_of is None:
+            if n_lists != n:
+                raise ValueError(f"{what}: without list_of there must be one list per item")
+        else:
+            list_of = np.ascontiguousarray(list_of, dtype=np.uint32)
+            _need(what + " list_of", list_of, n)
+        return online, offline, list_off, n_lists, list_of
+
+    def whitelist_verify_batch(self, sigs, lists_online, lists_offline, subs64, list_of=None, list_off=None):
+        """sigs: a list of serialised signatures (packed here) or the tuple (data, offsets[n+1]); lists_online / lists_offline: a list of
+        per-list byte strings of 64-byte secp256k1_pubkey objects, or -- with list_off[n_lists+1], counted in keys -- the packed arrays;
+        list_of[n]: each item's list (None: list i for item i); subs64: n*64.  What the C call refuses (a list_of entry out of range,
+        decreasing list_off) is refused there: S2KError."""
+        what = "whitelist_verify_batch"
+        if isinstance(sigs, tuple) and len(sigs) == 2:
+            data, off = _u8(sigs[0]), np.ascontiguousarray(sigs[1], dtype=np.uint64)
+        else:
+            data, off = Engine.pack([bytes(x) for x in sigs])
+        n = off.size - 1
+        _offsets_ok(what + " sigs", off, data.size)
+        subs64 = _u8(subs64); _need(what + " subs64", subs64, 64 * n)
+        online, offline, list_off, n_lists, list_of = self._whitelist_lists(what, lists_online, lists_offline, list_off, list_of, n)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_whitelist_verify_batch(self._h, _p(res), _p(data), _p(off), _p(online), _p(offline), _p(list_off), n_lists, _p(list_of),
+                                                               _p(subs64), n), "secp256k1_whitelist_verify_batch")
+        return res
+
+    def whitelist_verify_batch_dev(self, results, sigs, sig_off, online64, offline64, list_off, subs64, list_of=None, stream=None):
+        """results, sigs, online64, offline64, subs64 in HBM (torch tensors); sig_off[n+1], list_off[n_lists+1] and list_of[n] are HOST
+        arrays (numpy), read before the call returns"""
+        sig_off = np.ascontiguousarray(sig_off, dtype=np.uint64); list_off = np.ascontiguousarray(list_off, dtype=np.uint64)
+        n = sig_off.size - 1
+        if list_of is not None:
+            list_of = np.ascontiguousarray(list_of, dtype=np.uint32)
+            _need("whitelist_verify_batch_dev list_of", list_of, n)
+        self._check(self._lib.secp256k1_whitelist_verify_batch_dev(self._h, stream, _dp(results), _dp(sigs), _p(sig_off), _dp(online64), _dp(offline64), _p(list_off),
+                                                                   list_off.size - 1, _p(list_of), _dp(subs64), n), "secp256k1_whitelist_verify_batch_dev")
+
     def bppp_norm_product_verify_batch_dev(self, results, proofs, proof_len, transcripts, rho, gens33_dev, gens33_host, g_len, c_vec, c_vec_len, commits33, n,
                                            stream=None):
         """every array in HBM (torch uint8 tensors); gens33_host: the same generator set as a numpy array (cache key of the fixed-base table)"""

@@ -806,6 +806,26 @@ extern "C" int secp256k1_ecdsa_recover_amd(const void* ctx, void* pubkey, const 
     if (!secp256k1_ecdsa_recover_batch(e, &res, (unsigned char*)pubkey, sig64, o + 64, msghash32, 1)) { memset(pubkey, 0, 64); return 0; }
     return res;
 }
+// include/secp256k1_whitelist.h -- sig points at the secp256k1_whitelist_signature object {size_t n_keys; unsigned char data[32 * 256]},
+// the key arrays at n_keys 64-byte secp256k1_pubkey objects each (the kernels live in engine_whitelist.hip)
+extern "C" int secp256k1_whitelist_verify_amd(const void* ctx, const void* sig, const void* online_pubkeys, const void* offline_pubkeys, size_t n_keys,
+                                              const void* sub_pubkey) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!sig || !online_pubkeys || !offline_pubkeys || !sub_pubkey) return s2k_fail_arg("secp256k1_whitelist_verify_amd", "illegal argument (ARG_CHECK)");
+    size_t sig_keys; memcpy(&sig_keys, sig, sizeof(size_t));
+    if (sig_keys > 255 || sig_keys != n_keys) return 0;                                   // main_impl.h:112-114
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    std::vector<unsigned char> ser(1 + 32 * (sig_keys + 1));                              // secp256k1_whitelist_signature_serialize
+    ser[0] = (unsigned char)sig_keys;
+    memcpy(ser.data() + 1, (const unsigned char*)sig + sizeof(size_t), 32 * (sig_keys + 1));
+    const uint64_t sig_off[2] = {0, ser.size()}, list_off[2] = {0, n_keys};
+    int32_t res = 0;
+    if (!secp256k1_whitelist_verify_batch(e, &res, ser.data(), sig_off, (const unsigned char*)online_pubkeys, (const unsigned char*)offline_pubkeys, list_off, 1,
+                                          nullptr, (const unsigned char*)sub_pubkey, 1)) return 0;
+    return res;
+}
 // include/secp256k1_generator.h:190 -- arrays of pointers to 64-byte secp256k1_pedersen_commitment objects
 extern "C" int secp256k1_pedersen_verify_tally_amd(const void* ctx, const void* const* commits, size_t pcnt, const void* const* ncommits, size_t ncnt) {
     (void)ctx;
