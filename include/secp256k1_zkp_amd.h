@@ -235,6 +235,36 @@ S2K_API int secp256k1_whitelist_verify_batch_dev(s2k_engine* e, void* stream, in
                                                  const unsigned char* online64, const unsigned char* offline64, const uint64_t* list_off_host, size_t n_lists,
                                                  const uint32_t* list_of_host, const unsigned char* sub64, size_t n);
 
+/* ---- Taproot tweak checks ------------------------------------------------------------------------------------------
+ * results[i] = secp256k1_xonly_pubkey_tweak_add_check(ctx, tweaked32_i, parities[i], internal_i, tweak32_i)
+ *                                       (include/secp256k1_extrakeys.h, src/modules/extrakeys/main_impl.h:135-154)
+ * tweaked32 n*32: the serialised x-only output keys; parities n bytes (anything other than 0 or 1 gives 0: the reference compares
+ * the int); tweaks32 n*32 big-endian (>= n gives 0; 0 is legal and leaves the key as it is).
+ * key_format 0: internal_keys n*32 serialised x-only keys, accepted and refused as secp256k1_xonly_pubkey_parse does
+ *               (extrakeys/main_impl.h:22-42);
+ *            1: internal_keys n*64 `secp256k1_xonly_pubkey` opaque objects, read as they are (an all-zero object, where the
+ *               reference calls its illegal-argument callback, gives 0).
+ * NULL where the reference has ARG_CHECK or a key_format out of range is S2K_STATUS_ILLEGAL_ARGUMENT (return 0).
+ * _dev: every array in HBM; results is zeroed on the stream first. */
+S2K_API int secp256k1_xonly_pubkey_tweak_add_check_batch(s2k_engine* e, int32_t* results, const unsigned char* tweaked32, const unsigned char* parities,
+                                                         const unsigned char* internal_keys, int key_format, const unsigned char* tweaks32, size_t n);
+S2K_API int secp256k1_xonly_pubkey_tweak_add_check_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* tweaked32,
+                                                             const unsigned char* parities, const unsigned char* internal_keys, int key_format,
+                                                             const unsigned char* tweaks32, size_t n);
+/* ---- public-key tweak-add -------------------------------------------------------------------------------------------
+ * results[i] = secp256k1_xonly_pubkey_tweak_add(ctx, &pubkeys_out64[64 i], key_i, tweak32_i)     (key_format 0, 1)
+ *                                       (include/secp256k1_extrakeys.h, src/modules/extrakeys/main_impl.h:118-133)
+ *            = secp256k1_ec_pubkey_tweak_add(ctx, key_i -> &pubkeys_out64[64 i], tweak32_i)      (key_format 1, 2)
+ *                                       (include/secp256k1.h, src/secp256k1.c:766-790, src/eckey_impl.h:62-72)
+ * key_format 0 and 1 as above (1 is also the `secp256k1_pubkey` object: both load identically); 2: keys n*33 compressed keys,
+ * accepted and refused as secp256k1_ec_pubkey_parse does.  pubkeys_out64 n*64: `secp256k1_pubkey` objects, 64 zero bytes where
+ * results[i] == 0 (key refused, tweak >= n, or key + tweak G is the point at infinity).
+ * _dev: every array in HBM; results and pubkeys_out64 are zeroed on the stream first. */
+S2K_API int secp256k1_pubkey_tweak_add_batch(s2k_engine* e, int32_t* results, unsigned char* pubkeys_out64, const unsigned char* keys, int key_format,
+                                             const unsigned char* tweaks32, size_t n);
+S2K_API int secp256k1_pubkey_tweak_add_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* pubkeys_out64, const unsigned char* keys,
+                                                 int key_format, const unsigned char* tweaks32, size_t n);
+
 /* ---- half-aggregated Schnorr signature verification ------------------------------------------------------------------
  * *result = secp256k1_schnorrsig_aggverify(ctx, pubkeys, msgs32, n, aggsig, aggsig_len)
  *                                       (include/secp256k1_schnorrsig_halfagg.h, src/modules/schnorrsig_halfagg/main_impl.h:108-198)
@@ -329,6 +359,16 @@ S2K_API int secp256k1_ecdsa_recover_amd(const void* ctx, void* pubkey, const voi
  * secp256k1_pubkey objects each (they may be NULL when n_keys is 0 here; the reference's ARG_CHECK refuses that). */
 S2K_API int secp256k1_whitelist_verify_amd(const void* ctx, const void* sig, const void* online_pubkeys, const void* offline_pubkeys, size_t n_keys,
                                            const void* sub_pubkey);
+/*   secp256k1_xonly_pubkey_tweak_add_check(ctx, tweaked_pubkey32, tweaked_pk_parity, internal_pubkey, tweak32)
+ *                                                                   include/secp256k1_extrakeys.h, src/modules/extrakeys/main_impl.h:135
+ *   secp256k1_xonly_pubkey_tweak_add(ctx, output_pubkey, internal_pubkey, tweak32)          src/modules/extrakeys/main_impl.h:118
+ *   secp256k1_ec_pubkey_tweak_add(ctx, pubkey, tweak32)                                     src/secp256k1.c:773
+ * internal_pubkey: the 64-byte secp256k1_xonly_pubkey object; output_pubkey / pubkey: 64-byte secp256k1_pubkey objects (pubkey
+ * is read and written; both are zeroed on failure as the reference does).  A parity other than 0 or 1 gives 0 without a launch. */
+S2K_API int secp256k1_xonly_pubkey_tweak_add_check_amd(const void* ctx, const unsigned char* tweaked_pubkey32, int tweaked_pk_parity,
+                                                       const void* internal_pubkey, const unsigned char* tweak32);
+S2K_API int secp256k1_xonly_pubkey_tweak_add_amd(const void* ctx, void* output_pubkey, const void* internal_pubkey, const unsigned char* tweak32);
+S2K_API int secp256k1_ec_pubkey_tweak_add_amd(const void* ctx, void* pubkey, const unsigned char* tweak32);
 
 /* ---- Pedersen commitment tallies ------------------------------------------------------------------------------------
  * results[t] = secp256k1_pedersen_verify_tally(ctx, pos_t, pcnt_t, neg_t, ncnt_t)
@@ -440,6 +480,8 @@ S2K_API int secp256k1_schnorrsig_verify_batch_group(s2k_group* g, int32_t* resul
                                                     size_t msglen, const unsigned char* pubkeys, int pk_format, size_t n);
 S2K_API int secp256k1_ecdsa_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
                                                const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format, size_t n);
+S2K_API int secp256k1_xonly_pubkey_tweak_add_check_batch_group(s2k_group* g, int32_t* results, const unsigned char* tweaked32, const unsigned char* parities,
+                                                               const unsigned char* internal_keys, int key_format, const unsigned char* tweaks32, size_t n);
 S2K_API int s2k_ecmult_multi_group(s2k_group* g, unsigned char* r_xy, int32_t* r_inf, const unsigned char* g_sc, const unsigned char* sc,
                                    const unsigned char* pt_xy, const unsigned char* pt_inf, size_t n);
 S2K_API int s2k_ecmult_multi_group_dev(s2k_group* g, unsigned char* r_xy, int32_t* r_inf, const unsigned char* g_sc_dev0,

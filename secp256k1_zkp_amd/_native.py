@@ -46,6 +46,10 @@ SIGNATURES = {
     "secp256k1_ecdsa_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_recover_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "secp256k1_ecdsa_recover_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_xonly_pubkey_tweak_add_check_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_xonly_pubkey_tweak_add_check_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_pubkey_tweak_add_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_pubkey_tweak_add_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "secp256k1_whitelist_verify_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),
     "secp256k1_whitelist_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),
     "secp256k1_schnorrsig_aggverify_amd": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _sz, _vp, _sz]),
@@ -62,6 +66,9 @@ SIGNATURES = {
     "secp256k1_ecdsa_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "secp256k1_ecdsa_recover_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "secp256k1_whitelist_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _vp]),
+    "secp256k1_xonly_pubkey_tweak_add_check_amd": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _vp]),
+    "secp256k1_xonly_pubkey_tweak_add_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
+    "secp256k1_ec_pubkey_tweak_add_amd": (_c.c_int, [_vp, _vp, _vp]),
     "secp256k1_pedersen_verify_tally_amd": (_c.c_int, [_vp, _vp, _sz, _vp, _sz]),
     "secp256k1_surjectionproof_verify_amd": (_c.c_int, [_vp, _vp, _vp, _sz, _vp]),
     "secp256k1_surjectionproof_verify_batch": (_c.c_int, [_vp] + [_vp] * 6 + [_sz]),
@@ -83,6 +90,7 @@ SIGNATURES = {
     "secp256k1_rangeproof_verify_batch_ptrs_group": (_c.c_int, [_vp] + [_vp] * 9 + [_sz]),
     "secp256k1_schnorrsig_verify_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_verify_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_xonly_pubkey_tweak_add_check_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "s2k_ecmult_multi_group": (_c.c_int, [_vp] + [_vp] * 6 + [_sz]),
     "s2k_ecmult_multi_group_dev": (_c.c_int, [_vp] + [_vp] * 7),
 }

@@ -71,6 +71,21 @@ def _ecdsa_args(what, sigs, msghashes, pubkeys, sig_format, pk_format):
     return sigs, off, msghashes, pubkeys, n
 
 
+_TWEAK_KEY_BYTES = {0: 32, 1: 64, 2: 33}     # serialised x-only / secp256k1_xonly_pubkey or secp256k1_pubkey object / compressed
+
+
+def _tweak_check_args(what, tweaked32, parities, internal_keys, tweaks32, key_format):
+    """shape checks shared by Engine.xonly_tweak_add_check_batch and Group.xonly_tweak_add_check_batch"""
+    if key_format not in (0, 1):
+        raise ValueError(f"{what}: key_format must be 0 (n*32 x-only keys) or 1 (n*64 key objects)")
+    if tweaked32 is None or parities is None or internal_keys is None or tweaks32 is None:
+        raise ValueError(f"{what}: missing array")
+    tweaked32 = _u8(tweaked32); parities = _u8(parities); internal_keys = _u8(internal_keys); tweaks32 = _u8(tweaks32); n = tweaks32.size // 32
+    _need(what + " tweaks32", tweaks32, 32 * n); _need(what + " tweaked32", tweaked32, 32 * n); _need(what + " parities", parities, n)
+    _need(what + " internal_keys", internal_keys, _TWEAK_KEY_BYTES[key_format] * n)
+    return tweaked32, parities, internal_keys, tweaks32, n
+
+
 class Engine:
     """One engine per GPU/process (owns a stream, the generator table and an HBM workspace)."""
 
@@ -246,6 +261,39 @@ class Engine:
         n = sigs64.numel() // 64 if n is None else n
         self._check(self._lib.secp256k1_ecdsa_recover_batch_dev(self._h, stream, _dp(results), _dp(pubkeys_out64), _dp(sigs64), _dp(recids), _dp(msghashes), n),
                     "secp256k1_ecdsa_recover_batch_dev")
+
+    # ---- secp256k1_xonly_pubkey_tweak_add_check / _tweak_add (modules/extrakeys/main_impl.h:118-154) and secp256k1_ec_pubkey_tweak_add (secp256k1.c:766-790), batched ----
+    def xonly_tweak_add_check_batch(self, tweaked32, parities, internal_keys, tweaks32, key_format=0):
+        """key_format 0: n*32 serialised x-only internal keys, 1: n*64 secp256k1_xonly_pubkey objects; parities: one byte per item"""
+        tweaked32, parities, internal_keys, tweaks32, n = _tweak_check_args("xonly_tweak_add_check_batch", tweaked32, parities, internal_keys, tweaks32, key_format)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_xonly_pubkey_tweak_add_check_batch(self._h, _p(res), _p(tweaked32), _p(parities), _p(internal_keys), key_format, _p(tweaks32), n),
+                    "secp256k1_xonly_pubkey_tweak_add_check_batch")
+        return res
+
+    def xonly_tweak_add_check_batch_dev(self, results, tweaked32, parities, internal_keys, tweaks32, key_format=0, n=None, stream=None):
+        """every array in HBM (torch tensors)"""
+        n = tweaks32.numel() // 32 if n is None else n
+        self._check(self._lib.secp256k1_xonly_pubkey_tweak_add_check_batch_dev(self._h, stream, _dp(results), _dp(tweaked32), _dp(parities), _dp(internal_keys), key_format,
+                                                                               _dp(tweaks32), n), "secp256k1_xonly_pubkey_tweak_add_check_batch_dev")
+
+    def pubkey_tweak_add_batch(self, keys, tweaks32, key_format=1):
+        """key_format 0: n*32 x-only keys, 1: n*64 key objects, 2: n*33 compressed keys
+        -> (results[n], pubkeys64[n, 64]): secp256k1_pubkey objects (key_format 1 reads them), zero where results[i] == 0"""
+        if key_format not in _TWEAK_KEY_BYTES:
+            raise ValueError("pubkey_tweak_add_batch: key_format must be 0, 1 or 2")
+        if keys is None or tweaks32 is None:
+            raise ValueError("pubkey_tweak_add_batch: missing array")
+        keys = _u8(keys); tweaks32 = _u8(tweaks32); n = tweaks32.size // 32
+        _need("pubkey_tweak_add_batch tweaks32", tweaks32, 32 * n); _need("pubkey_tweak_add_batch keys", keys, _TWEAK_KEY_BYTES[key_format] * n)
+        res = np.zeros(n, np.int32); pk = np.zeros((n, 64), np.uint8)
+        self._check(self._lib.secp256k1_pubkey_tweak_add_batch(self._h, _p(res), _p(pk), _p(keys), key_format, _p(tweaks32), n), "secp256k1_pubkey_tweak_add_batch")
+        return res, pk
+
+    def pubkey_tweak_add_batch_dev(self, results, pubkeys_out64, keys, tweaks32, key_format=1, n=None, stream=None):
+        n = tweaks32.numel() // 32 if n is None else n
+        self._check(self._lib.secp256k1_pubkey_tweak_add_batch_dev(self._h, stream, _dp(results), _dp(pubkeys_out64), _dp(keys), key_format, _dp(tweaks32), n),
+                    "secp256k1_pubkey_tweak_add_batch_dev")
 
     # ---- secp256k1_whitelist_signature_parse + secp256k1_whitelist_verify (modules/whitelist/main_impl.h:99-151), batched ----
     @staticmethod
@@ -538,6 +586,13 @@ class Group:
         res = np.zeros(n, np.int32)
         self._check(self._lib.secp256k1_ecdsa_verify_batch_group(self._h, _p(res), _p(sigs), _p(off), sig_format, _p(msghashes), _p(pubkeys), pk_format, n),
                     "secp256k1_ecdsa_verify_batch_group")
+        return res
+
+    def xonly_tweak_add_check_batch(self, tweaked32, parities, internal_keys, tweaks32, key_format=0):
+        tweaked32, parities, internal_keys, tweaks32, n = _tweak_check_args("xonly_tweak_add_check_batch_group", tweaked32, parities, internal_keys, tweaks32, key_format)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_xonly_pubkey_tweak_add_check_batch_group(self._h, _p(res), _p(tweaked32), _p(parities), _p(internal_keys), key_format,
+                                                                                  _p(tweaks32), n), "secp256k1_xonly_pubkey_tweak_add_check_batch_group")
         return res
 
     def ecmult_multi(self, sc, pt_xy, g_sc=None, pt_inf=None):

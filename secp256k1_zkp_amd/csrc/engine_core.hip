@@ -826,6 +826,46 @@ extern "C" int secp256k1_whitelist_verify_amd(const void* ctx, const void* sig, 
                                           nullptr, (const unsigned char*)sub_pubkey, 1)) return 0;
     return res;
 }
+// include/secp256k1_extrakeys.h (src/modules/extrakeys/main_impl.h:135) -- internal_pubkey points at the 64-byte secp256k1_xonly_pubkey
+// object (the kernels live in engine_tweak.hip)
+extern "C" int secp256k1_xonly_pubkey_tweak_add_check_amd(const void* ctx, const unsigned char* tweaked_pubkey32, int tweaked_pk_parity, const void* internal_pubkey,
+                                                          const unsigned char* tweak32) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!internal_pubkey || !tweaked_pubkey32 || !tweak32) return s2k_fail_arg("secp256k1_xonly_pubkey_tweak_add_check_amd", "illegal argument (ARG_CHECK)");
+    if (tweaked_pk_parity != 0 && tweaked_pk_parity != 1) return 0;                       // main_impl.h:153 compares the int: no point can match
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0; const unsigned char par = (unsigned char)tweaked_pk_parity;
+    if (!secp256k1_xonly_pubkey_tweak_add_check_batch(e, &res, tweaked_pubkey32, &par, (const unsigned char*)internal_pubkey, 1, tweak32, 1)) return 0;
+    return res;
+}
+// src/modules/extrakeys/main_impl.h:118 -- output_pubkey receives a secp256k1_pubkey object (zeroed first, as :123)
+extern "C" int secp256k1_xonly_pubkey_tweak_add_amd(const void* ctx, void* output_pubkey, const void* internal_pubkey, const unsigned char* tweak32) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!output_pubkey) return s2k_fail_arg("secp256k1_xonly_pubkey_tweak_add_amd", "illegal argument (ARG_CHECK)");
+    memset(output_pubkey, 0, 64);
+    if (!internal_pubkey || !tweak32) return s2k_fail_arg("secp256k1_xonly_pubkey_tweak_add_amd", "illegal argument (ARG_CHECK)");
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0;
+    if (!secp256k1_pubkey_tweak_add_batch(e, &res, (unsigned char*)output_pubkey, (const unsigned char*)internal_pubkey, 1, tweak32, 1)) { memset(output_pubkey, 0, 64); return 0; }
+    return res;
+}
+// src/secp256k1.c:773 -- pubkey is read and written; zeroed on failure (:781-782 clears it before the tweak is tried)
+extern "C" int secp256k1_ec_pubkey_tweak_add_amd(const void* ctx, void* pubkey, const unsigned char* tweak32) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!pubkey || !tweak32) return s2k_fail_arg("secp256k1_ec_pubkey_tweak_add_amd", "illegal argument (ARG_CHECK)");
+    unsigned char in[64]; memcpy(in, pubkey, 64);
+    memset(pubkey, 0, 64);
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0;
+    if (!secp256k1_pubkey_tweak_add_batch(e, &res, (unsigned char*)pubkey, in, 1, tweak32, 1)) { memset(pubkey, 0, 64); return 0; }
+    return res;
+}
 // include/secp256k1_generator.h:190 -- arrays of pointers to 64-byte secp256k1_pedersen_commitment objects
 extern "C" int secp256k1_pedersen_verify_tally_amd(const void* ctx, const void* const* commits, size_t pcnt, const void* const* ncommits, size_t ncnt) {
     (void)ctx;
@@ -1146,6 +1186,29 @@ extern "C" int secp256k1_ecdsa_verify_batch_group(s2k_group* g, int32_t* results
             if (hi == lo) return 1;
             return secp256k1_ecdsa_verify_batch(e, results + lo, der ? sigs : sigs + 64 * lo, der ? sig_off + lo : nullptr, sig_format, msghash32 + 32 * lo,
                                                 pubkeys + pkb * lo, pk_format, hi - lo);
+        };
+    }
+    const int ok = group_run(g, jobs);
+    if (!ok) memset(results, 0, sizeof(int32_t) * n);
+    return ok;
+}
+extern "C" int secp256k1_xonly_pubkey_tweak_add_check_batch_group(s2k_group* g, int32_t* results, const unsigned char* tweaked32, const unsigned char* parities,
+                                                                  const unsigned char* internal_keys, int key_format, const unsigned char* tweaks32, size_t n) {
+    const char* who = "secp256k1_xonly_pubkey_tweak_add_check_batch_group";
+    if (!g || g->eng.empty()) return s2k_fail(who, "null group");
+    if (n == 0) return 1;
+    if (!results || !tweaked32 || !parities || !internal_keys || !tweaks32) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    if (key_format < 0 || key_format > 1) return s2k_fail_arg(who, "key_format must be 0 (x-only, 32 bytes) or 1 (object)");
+    std::lock_guard<std::mutex> call(g->call_mu);
+    memset(results, 0, sizeof(int32_t) * n);
+    const size_t k = g->eng.size(), kb = key_format ? 64 : 32;
+    std::vector<std::function<int()>> jobs(k);
+    for (size_t i = 0; i < k; i++) {
+        size_t lo, hi; group_share(n, k, i, lo, hi);
+        s2k_engine* e = g->eng[i];
+        jobs[i] = [=]() -> int {
+            if (hi == lo) return 1;
+            return secp256k1_xonly_pubkey_tweak_add_check_batch(e, results + lo, tweaked32 + 32 * lo, parities + lo, internal_keys + kb * lo, key_format, tweaks32 + 32 * lo, hi - lo);
         };
     }
     const int ok = group_run(g, jobs);
