@@ -265,6 +265,49 @@ S2K_API int secp256k1_pubkey_tweak_add_batch(s2k_engine* e, int32_t* results, un
 S2K_API int secp256k1_pubkey_tweak_add_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* pubkeys_out64, const unsigned char* keys,
                                                  int key_format, const unsigned char* tweaks32, size_t n);
 
+/* ---- asset generators ----------------------------------------------------------------------------------------------
+ * PUBLIC INPUTS ONLY: nothing below is constant time.  A blind handed to these functions is treated as public data (the
+ * reference's generate_blinded and pedersen_commit are secret-key paths; here they serve explicit amounts, blind 0, and the
+ * re-derivation of public objects).
+ *
+ * results[i] = secp256k1_generator_generate(ctx, &gens_out64[64 i], key32_i)                          (blinds32 NULL)
+ *            = secp256k1_generator_generate_blinded(ctx, &gens_out64[64 i], key32_i, blind32_i)       (blinds32 n*32)
+ *                                       (include/secp256k1_generator.h, src/modules/generator/main_impl.h:204-264; the map
+ *                                        shallue_van_de_woestijne :94-202)
+ * gens_out64 n*64: `secp256k1_generator` opaque objects, byte for byte the reference's.  Where results[i] == 0 -- a blind >= n --
+ * the object is 64 zero bytes: the reference writes a generator from the reduced blind and returns 0, the engine does not.
+ * (A key whose two mapped points are opposite, which no hash reaches and where the reference is undefined, gives 0 and zeros too.
+ * So does a key one of whose two hashes is >= p, about 2^-128 per key: the reference returns 0 there as well but still writes a
+ * generator.) */
+S2K_API int secp256k1_generator_generate_batch(s2k_engine* e, int32_t* results, unsigned char* gens_out64, const unsigned char* keys32,
+                                               const unsigned char* blinds32, size_t n);
+S2K_API int secp256k1_generator_generate_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* gens_out64, const unsigned char* keys32,
+                                                   const unsigned char* blinds32, size_t n);
+/* results[i] = secp256k1_generator_parse(ctx, &gens_out64[64 i], &gens33[33 i])            (src/modules/generator/main_impl.h:59-77)
+ * gens33 n*33: prefix 0x0a / 0x0b, then x.  Any other prefix, x >= p or x off the curve gives 0 and 64 zero bytes.
+ * out33[33 i ..] = what secp256k1_generator_serialize(ctx, out, &gens64[64 i]) writes: 11 ^ is_square(y), then x    (:79-92)
+ * NULL where the reference has ARG_CHECK is S2K_STATUS_ILLEGAL_ARGUMENT (return 0); n == 0 returns 1.
+ * _dev: every array in HBM; results and the outputs are zeroed on the stream first. */
+S2K_API int secp256k1_generator_parse_batch(s2k_engine* e, int32_t* results, unsigned char* gens_out64, const unsigned char* gens33, size_t n);
+S2K_API int secp256k1_generator_parse_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* gens_out64, const unsigned char* gens33, size_t n);
+S2K_API int secp256k1_generator_serialize_batch(s2k_engine* e, unsigned char* out33, const unsigned char* gens64, size_t n);
+S2K_API int secp256k1_generator_serialize_batch_dev(s2k_engine* e, void* stream, unsigned char* out33, const unsigned char* gens64, size_t n);
+/* ---- Pedersen commitments to public amounts -----------------------------------------------------------------------------
+ * results[i] = secp256k1_pedersen_commit(ctx, &commit, blind32_i, values[i], &gens64[64 i])
+ *                                       (src/modules/generator/main_impl.h:309-335, src/modules/generator/pedersen_impl.h:42-49)
+ * commits_out33 n*33: the first 33 bytes of the commitment object (its serialisation): 9 ^ is_square(y), then x -- what
+ * secp256k1_pedersen_verify_tally_batch takes.  blinds32 NULL: all-zero blinds, the explicit-amount case
+ * (secp256k1_pedersen_commit(ctx, &c, zero_blind, value, &gen)); no fixed-base work is done then.
+ * results[i] == 0 with 33 zero bytes: blind >= n, or the point at infinity (blind 0 with value 0; blind G = -value gen).
+ * Generator objects are read as they are: one that is not on the curve is the caller's error, as in the reference, and the error
+ * stays with its item.  The all-zero object -- what the parse and generate forms above write for a refused item -- and any other
+ * object with y = 0 are refused: results[i] == 0 and 33 zero bytes, whatever value and blind are.  Other off-curve objects give
+ * some 33 bytes, or 0 and zero bytes.  The other items of the batch are never affected. */
+S2K_API int secp256k1_pedersen_commit_batch(s2k_engine* e, int32_t* results, unsigned char* commits_out33, const unsigned char* blinds32,
+                                            const uint64_t* values, const unsigned char* gens64, size_t n);
+S2K_API int secp256k1_pedersen_commit_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* commits_out33, const unsigned char* blinds32,
+                                                const uint64_t* values, const unsigned char* gens64, size_t n);
+
 /* ---- half-aggregated Schnorr signature verification ------------------------------------------------------------------
  * *result = secp256k1_schnorrsig_aggverify(ctx, pubkeys, msgs32, n, aggsig, aggsig_len)
  *                                       (include/secp256k1_schnorrsig_halfagg.h, src/modules/schnorrsig_halfagg/main_impl.h:108-198)
@@ -369,6 +412,14 @@ S2K_API int secp256k1_xonly_pubkey_tweak_add_check_amd(const void* ctx, const un
                                                        const void* internal_pubkey, const unsigned char* tweak32);
 S2K_API int secp256k1_xonly_pubkey_tweak_add_amd(const void* ctx, void* output_pubkey, const void* internal_pubkey, const unsigned char* tweak32);
 S2K_API int secp256k1_ec_pubkey_tweak_add_amd(const void* ctx, void* pubkey, const unsigned char* tweak32);
+/*   secp256k1_generator_generate(ctx, gen, key32)                                  src/modules/generator/main_impl.h:250
+ *   secp256k1_generator_parse(ctx, gen, input)                                     src/modules/generator/main_impl.h:59
+ *   secp256k1_pedersen_commit(ctx, commit, blind, value, gen)                      src/modules/generator/main_impl.h:309
+ * gen: the 64-byte secp256k1_generator object; commit: the 64-byte secp256k1_pedersen_commitment object, of which the first 33
+ * bytes are written and the rest zeroed.  Outputs are zeroed on failure.  The blind is treated as public data (see above). */
+S2K_API int secp256k1_generator_generate_amd(const void* ctx, void* gen, const unsigned char* key32);
+S2K_API int secp256k1_generator_parse_amd(const void* ctx, void* gen, const unsigned char* input33);
+S2K_API int secp256k1_pedersen_commit_amd(const void* ctx, void* commit, const unsigned char* blind, uint64_t value, const void* gen);
 
 /* ---- Pedersen commitment tallies ------------------------------------------------------------------------------------
  * results[t] = secp256k1_pedersen_verify_tally(ctx, pos_t, pcnt_t, neg_t, ncnt_t)

@@ -50,6 +50,14 @@ SIGNATURES = {
     "secp256k1_xonly_pubkey_tweak_add_check_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "secp256k1_pubkey_tweak_add_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "secp256k1_pubkey_tweak_add_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_generator_generate_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_generator_generate_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_generator_parse_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_generator_parse_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_generator_serialize_batch": (_c.c_int, [_vp, _vp, _vp, _sz]),
+    "secp256k1_generator_serialize_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_pedersen_commit_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_pedersen_commit_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "secp256k1_whitelist_verify_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),
     "secp256k1_whitelist_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),
     "secp256k1_schnorrsig_aggverify_amd": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _sz, _vp, _sz]),
@@ -69,6 +77,9 @@ SIGNATURES = {
     "secp256k1_xonly_pubkey_tweak_add_check_amd": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _vp]),
     "secp256k1_xonly_pubkey_tweak_add_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "secp256k1_ec_pubkey_tweak_add_amd": (_c.c_int, [_vp, _vp, _vp]),
+    "secp256k1_generator_generate_amd": (_c.c_int, [_vp, _vp, _vp]),
+    "secp256k1_generator_parse_amd": (_c.c_int, [_vp, _vp, _vp]),
+    "secp256k1_pedersen_commit_amd": (_c.c_int, [_vp, _vp, _vp, _c.c_uint64, _vp]),
     "secp256k1_pedersen_verify_tally_amd": (_c.c_int, [_vp, _vp, _sz, _vp, _sz]),
     "secp256k1_surjectionproof_verify_amd": (_c.c_int, [_vp, _vp, _vp, _sz, _vp]),
     "secp256k1_surjectionproof_verify_batch": (_c.c_int, [_vp] + [_vp] * 6 + [_sz]),

@@ -295,6 +295,73 @@ class Engine:
         self._check(self._lib.secp256k1_pubkey_tweak_add_batch_dev(self._h, stream, _dp(results), _dp(pubkeys_out64), _dp(keys), key_format, _dp(tweaks32), n),
                     "secp256k1_pubkey_tweak_add_batch_dev")
 
+    # ---- secp256k1_generator_generate[_blinded] / _parse / _serialize and secp256k1_pedersen_commit (modules/generator/main_impl.h:59-335), batched.
+    #      Public inputs only: blinds are treated as public data (nothing is constant time). ----
+    def generator_generate_batch(self, keys32, blinds32=None):
+        """keys32: n*32 asset ids; blinds32: None or n*32 -> (results[n], gens64[n, 64]): secp256k1_generator objects, zero where results[i] == 0"""
+        if keys32 is None:
+            raise ValueError("generator_generate_batch: missing array")
+        keys32 = _u8(keys32); n = keys32.size // 32
+        _need("generator_generate_batch keys32", keys32, 32 * n)
+        if blinds32 is not None:
+            blinds32 = _u8(blinds32); _need("generator_generate_batch blinds32", blinds32, 32 * n)
+        res = np.zeros(n, np.int32); gens = np.zeros((n, 64), np.uint8)
+        self._check(self._lib.secp256k1_generator_generate_batch(self._h, _p(res), _p(gens), _p(keys32), _p(blinds32), n), "secp256k1_generator_generate_batch")
+        return res, gens
+
+    def generator_generate_batch_dev(self, results, gens_out64, keys32, blinds32=None, n=None, stream=None):
+        """every array in HBM (torch tensors); blinds32 may be None"""
+        n = keys32.numel() // 32 if n is None else n
+        self._check(self._lib.secp256k1_generator_generate_batch_dev(self._h, stream, _dp(results), _dp(gens_out64), _dp(keys32), _dp(blinds32), n),
+                    "secp256k1_generator_generate_batch_dev")
+
+    def generator_parse_batch(self, gens33):
+        """gens33: n*33 serialised generators (0x0a / 0x0b, x) -> (results[n], gens64[n, 64]), zero where refused"""
+        if gens33 is None:
+            raise ValueError("generator_parse_batch: missing array")
+        gens33 = _u8(gens33); n = gens33.size // 33
+        _need("generator_parse_batch gens33", gens33, 33 * n)
+        res = np.zeros(n, np.int32); gens = np.zeros((n, 64), np.uint8)
+        self._check(self._lib.secp256k1_generator_parse_batch(self._h, _p(res), _p(gens), _p(gens33), n), "secp256k1_generator_parse_batch")
+        return res, gens
+
+    def generator_parse_batch_dev(self, results, gens_out64, gens33, n=None, stream=None):
+        n = gens33.numel() // 33 if n is None else n
+        self._check(self._lib.secp256k1_generator_parse_batch_dev(self._h, stream, _dp(results), _dp(gens_out64), _dp(gens33), n), "secp256k1_generator_parse_batch_dev")
+
+    def generator_serialize_batch(self, gens64):
+        """gens64: n*64 secp256k1_generator objects -> out33[n, 33]"""
+        if gens64 is None:
+            raise ValueError("generator_serialize_batch: missing array")
+        gens64 = _u8(gens64); n = gens64.size // 64
+        _need("generator_serialize_batch gens64", gens64, 64 * n)
+        out = np.zeros((n, 33), np.uint8)
+        self._check(self._lib.secp256k1_generator_serialize_batch(self._h, _p(out), _p(gens64), n), "secp256k1_generator_serialize_batch")
+        return out
+
+    def generator_serialize_batch_dev(self, out33, gens64, n=None, stream=None):
+        n = gens64.numel() // 64 if n is None else n
+        self._check(self._lib.secp256k1_generator_serialize_batch_dev(self._h, stream, _dp(out33), _dp(gens64), n), "secp256k1_generator_serialize_batch_dev")
+
+    def pedersen_commit_batch(self, values, gens64, blinds32=None):
+        """values: n uint64; gens64: n*64 generator objects; blinds32: None (all-zero blinds: explicit amounts) or n*32
+        -> (results[n], commits33[n, 33]): serialised commitments, zero where results[i] == 0"""
+        if values is None or gens64 is None:
+            raise ValueError("pedersen_commit_batch: missing array")
+        values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1); n = values.size
+        gens64 = _u8(gens64); _need("pedersen_commit_batch gens64", gens64, 64 * n)
+        if blinds32 is not None:
+            blinds32 = _u8(blinds32); _need("pedersen_commit_batch blinds32", blinds32, 32 * n)
+        res = np.zeros(n, np.int32); out = np.zeros((n, 33), np.uint8)
+        self._check(self._lib.secp256k1_pedersen_commit_batch(self._h, _p(res), _p(out), _p(blinds32), _p(values), _p(gens64), n), "secp256k1_pedersen_commit_batch")
+        return res, out
+
+    def pedersen_commit_batch_dev(self, results, commits_out33, values, gens64, blinds32=None, n=None, stream=None):
+        """every array in HBM (torch tensors; values int64 or uint64 bit patterns); blinds32 may be None"""
+        n = values.numel() if n is None else n
+        self._check(self._lib.secp256k1_pedersen_commit_batch_dev(self._h, stream, _dp(results), _dp(commits_out33), _dp(blinds32), _dp(values), _dp(gens64), n),
+                    "secp256k1_pedersen_commit_batch_dev")
+
     # ---- secp256k1_whitelist_signature_parse + secp256k1_whitelist_verify (modules/whitelist/main_impl.h:99-151), batched ----
     @staticmethod
     def _whitelist_lists(what, lists_online, lists_offline, list_off, list_of, n):

@@ -866,6 +866,46 @@ extern "C" int secp256k1_ec_pubkey_tweak_add_amd(const void* ctx, void* pubkey, 
     if (!secp256k1_pubkey_tweak_add_batch(e, &res, (unsigned char*)pubkey, in, 1, tweak32, 1)) { memset(pubkey, 0, 64); return 0; }
     return res;
 }
+// src/modules/generator/main_impl.h:250 -- gen receives a secp256k1_generator object (the kernels live in engine_generator.hip)
+extern "C" int secp256k1_generator_generate_amd(const void* ctx, void* gen, const unsigned char* key32) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!gen) return s2k_fail_arg("secp256k1_generator_generate_amd", "illegal argument (ARG_CHECK)");
+    memset(gen, 0, 64);
+    if (!key32) return s2k_fail_arg("secp256k1_generator_generate_amd", "illegal argument (ARG_CHECK)");
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0;
+    if (!secp256k1_generator_generate_batch(e, &res, (unsigned char*)gen, key32, nullptr, 1)) { memset(gen, 0, 64); return 0; }
+    return res;
+}
+// src/modules/generator/main_impl.h:59
+extern "C" int secp256k1_generator_parse_amd(const void* ctx, void* gen, const unsigned char* input33) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!gen) return s2k_fail_arg("secp256k1_generator_parse_amd", "illegal argument (ARG_CHECK)");
+    memset(gen, 0, 64);
+    if (!input33) return s2k_fail_arg("secp256k1_generator_parse_amd", "illegal argument (ARG_CHECK)");
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0;
+    if (!secp256k1_generator_parse_batch(e, &res, (unsigned char*)gen, input33, 1)) { memset(gen, 0, 64); return 0; }
+    return res;
+}
+// src/modules/generator/main_impl.h:309 -- commit receives the first 33 bytes of a secp256k1_pedersen_commitment object, the rest zeroed.
+// The blind is treated as public data: nothing here is constant time.
+extern "C" int secp256k1_pedersen_commit_amd(const void* ctx, void* commit, const unsigned char* blind, uint64_t value, const void* gen) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!commit) return s2k_fail_arg("secp256k1_pedersen_commit_amd", "illegal argument (ARG_CHECK)");
+    memset(commit, 0, 64);
+    if (!blind || !gen) return s2k_fail_arg("secp256k1_pedersen_commit_amd", "illegal argument (ARG_CHECK)");
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0;
+    if (!secp256k1_pedersen_commit_batch(e, &res, (unsigned char*)commit, blind, &value, (const unsigned char*)gen, 1)) { memset(commit, 0, 64); return 0; }
+    return res;
+}
 // include/secp256k1_generator.h:190 -- arrays of pointers to 64-byte secp256k1_pedersen_commitment objects
 extern "C" int secp256k1_pedersen_verify_tally_amd(const void* ctx, const void* const* commits, size_t pcnt, const void* const* ncommits, size_t ncnt) {
     (void)ctx;
