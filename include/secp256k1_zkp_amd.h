@@ -139,6 +139,15 @@ S2K_API int s2k_ecmult_batch(s2k_engine* e, unsigned char* r_xy, int32_t* r_inf,
                              const unsigned char* a_inf, const unsigned char* na, const unsigned char* ng, size_t n);
 S2K_API int s2k_ecmult_batch_dev(s2k_engine* e, void* stream, unsigned char* r_xy, int32_t* r_inf, const unsigned char* a_xy,
                                  const unsigned char* a_inf, const unsigned char* na, const unsigned char* ng, size_t n);
+/* r[i] = na[i]*A[i] + nb[i]*B[i]       two variable points, no generator term: what the reference takes two secp256k1_ecmult calls and a
+ *                                       secp256k1_gej_add_var for (e.g. src/modules/ecdsa_adaptor/dleq_impl.h:146-150).  The GLV halves
+ *                                       of both scalars share one chain of 128 doublings (csrc/ecmult.h: ecmult_lane2); a wavefront
+ *                                       with an infinite point, a zero scalar or an exceptional addition takes the two-call form.
+ * a_xy, b_xy: n*64; a_inf, b_inf: n bytes or NULL (all finite); na, nb: n*32.  Outputs as s2k_ecmult_batch. */
+S2K_API int s2k_ecmult2_batch(s2k_engine* e, unsigned char* r_xy, int32_t* r_inf, const unsigned char* a_xy, const unsigned char* a_inf,
+                              const unsigned char* na, const unsigned char* b_xy, const unsigned char* b_inf, const unsigned char* nb, size_t n);
+S2K_API int s2k_ecmult2_batch_dev(s2k_engine* e, void* stream, unsigned char* r_xy, int32_t* r_inf, const unsigned char* a_xy, const unsigned char* a_inf,
+                                  const unsigned char* na, const unsigned char* b_xy, const unsigned char* b_inf, const unsigned char* nb, size_t n);
 
 /* ---- multi-scalar multiplication ------------------------------------------------------------------------------
  * r = g_sc*G + sum_i sc[i]*pt[i]        replaces: static int secp256k1_ecmult_multi_var(const secp256k1_callback*,
@@ -212,6 +221,20 @@ S2K_API int secp256k1_ecdsa_recover_batch(s2k_engine* e, int32_t* results, unsig
                                           const unsigned char* recids, const unsigned char* msghash32, size_t n);
 S2K_API int secp256k1_ecdsa_recover_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* pubkeys_out64, const unsigned char* sigs64,
                                               const unsigned char* recids, const unsigned char* msghash32, size_t n);
+
+/* ---- ECDSA adaptor-signature batch verification ---------------------------------------------------------------------
+ * results[i] = public key_i and encryption key_i parse &&
+ *              secp256k1_ecdsa_adaptor_verify(ctx, adaptor_sigs162 + 162 i, pubkey_i, msgs32 + 32 i, enckey_i)
+ *                                       (include/secp256k1_ecdsa_adaptor.h, src/modules/ecdsa_adaptor/main_impl.h:236-282;
+ *                                        the DLEQ proof: src/modules/ecdsa_adaptor/dleq_impl.h:131-162)
+ * adaptor_sigs162 n*162: R | R' | s' | e | s as secp256k1_ecdsa_adaptor_encrypt writes them; msgs32 n*32.  pk_format as in the ECDSA
+ * calls (0: n*33 compressed, 1: n*64 `secp256k1_pubkey` objects, an all-zero x giving 0, 2: n*65 uncompressed or hybrid); pubkeys and
+ * enckeys share it.  Only verification is served: it reads public data.  Encrypt, decrypt and recover handle secrets and need the
+ * reference's constant-time code. */
+S2K_API int secp256k1_ecdsa_adaptor_verify_batch(s2k_engine* e, int32_t* results, const unsigned char* adaptor_sigs162, const unsigned char* pubkeys,
+                                                 const unsigned char* msgs32, const unsigned char* enckeys, int pk_format, size_t n);
+S2K_API int secp256k1_ecdsa_adaptor_verify_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* adaptor_sigs162,
+                                                     const unsigned char* pubkeys, const unsigned char* msgs32, const unsigned char* enckeys, int pk_format, size_t n);
 
 /* ---- Whitelist-signature batch verification -------------------------------------------------------------------------
  * results[i] = secp256k1_whitelist_signature_parse(ctx, &sig, sigs + sig_off[i], sig_off[i+1] - sig_off[i]) &&
@@ -397,6 +420,11 @@ S2K_API int secp256k1_surjectionproof_verify_amd(const void* ctx, const void* pr
  * r and s, then the recovery id); pubkey: the 64-byte secp256k1_pubkey object (written by the recovery form: zeroed on failure). */
 S2K_API int secp256k1_ecdsa_verify_amd(const void* ctx, const void* sig, const unsigned char* msghash32, const void* pubkey);
 S2K_API int secp256k1_ecdsa_recover_amd(const void* ctx, void* pubkey, const void* signature, const unsigned char* msghash32);
+/*   secp256k1_ecdsa_adaptor_verify(ctx, adaptor_sig162, pubkey, msg32, enckey)         include/secp256k1_ecdsa_adaptor.h,
+ *                                                                                      src/modules/ecdsa_adaptor/main_impl.h:236
+ * pubkey, enckey: 64-byte secp256k1_pubkey objects. */
+S2K_API int secp256k1_ecdsa_adaptor_verify_amd(const void* ctx, const unsigned char* adaptor_sig162, const void* pubkey, const unsigned char* msg32,
+                                               const void* enckey);
 /*   secp256k1_whitelist_verify(ctx, sig, online_pubkeys, offline_pubkeys, n_keys, sub_pubkey)      include/secp256k1_whitelist.h
  * sig: the secp256k1_whitelist_signature object {size_t n_keys; unsigned char data[32 * 256]}; the key arrays: n_keys 64-byte
  * secp256k1_pubkey objects each (they may be NULL when n_keys is 0 here; the reference's ARG_CHECK refuses that). */
@@ -531,6 +559,8 @@ S2K_API int secp256k1_schnorrsig_verify_batch_group(s2k_group* g, int32_t* resul
                                                     size_t msglen, const unsigned char* pubkeys, int pk_format, size_t n);
 S2K_API int secp256k1_ecdsa_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
                                                const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format, size_t n);
+S2K_API int secp256k1_ecdsa_adaptor_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* adaptor_sigs162, const unsigned char* pubkeys,
+                                                       const unsigned char* msgs32, const unsigned char* enckeys, int pk_format, size_t n);
 S2K_API int secp256k1_xonly_pubkey_tweak_add_check_batch_group(s2k_group* g, int32_t* results, const unsigned char* tweaked32, const unsigned char* parities,
                                                                const unsigned char* internal_keys, int key_format, const unsigned char* tweaks32, size_t n);
 S2K_API int s2k_ecmult_multi_group(s2k_group* g, unsigned char* r_xy, int32_t* r_inf, const unsigned char* g_sc, const unsigned char* sc,

@@ -33,6 +33,8 @@ SIGNATURES = {
     "s2k_engine_rp_handback": (_c.c_int, [_vp, _vp]),
     "s2k_ecmult_batch": (_c.c_int, [_vp] + [_vp] * 6 + [_sz]),
     "s2k_ecmult_batch_dev": (_c.c_int, [_vp, _vp] + [_vp] * 6 + [_sz]),
+    "s2k_ecmult2_batch": (_c.c_int, [_vp] + [_vp] * 8 + [_sz]),
+    "s2k_ecmult2_batch_dev": (_c.c_int, [_vp, _vp] + [_vp] * 8 + [_sz]),
     "s2k_ecmult_multi": (_c.c_int, [_vp] + [_vp] * 6 + [_sz]),
     "s2k_ecmult_multi_dev": (_c.c_int, [_vp, _vp] + [_vp] * 6 + [_sz]),
     "s2k_ecmult_multi_partial_dev": (_c.c_int, [_vp, _vp] + [_vp] * 5 + [_sz]),
@@ -46,6 +48,8 @@ SIGNATURES = {
     "secp256k1_ecdsa_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_recover_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "secp256k1_ecdsa_recover_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_ecdsa_adaptor_verify_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_ecdsa_adaptor_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_xonly_pubkey_tweak_add_check_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "secp256k1_xonly_pubkey_tweak_add_check_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "secp256k1_pubkey_tweak_add_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
@@ -73,6 +77,7 @@ SIGNATURES = {
     "secp256k1_schnorrsig_verify_amd": (_c.c_int, [_vp, _vp, _vp, _sz, _vp]),
     "secp256k1_ecdsa_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "secp256k1_ecdsa_recover_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
+    "secp256k1_ecdsa_adaptor_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "secp256k1_whitelist_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _vp]),
     "secp256k1_xonly_pubkey_tweak_add_check_amd": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _vp]),
     "secp256k1_xonly_pubkey_tweak_add_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
@@ -101,6 +106,7 @@ SIGNATURES = {
     "secp256k1_rangeproof_verify_batch_ptrs_group": (_c.c_int, [_vp] + [_vp] * 9 + [_sz]),
     "secp256k1_schnorrsig_verify_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_verify_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_ecdsa_adaptor_verify_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_xonly_pubkey_tweak_add_check_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "s2k_ecmult_multi_group": (_c.c_int, [_vp] + [_vp] * 6 + [_sz]),
     "s2k_ecmult_multi_group_dev": (_c.c_int, [_vp] + [_vp] * 7),

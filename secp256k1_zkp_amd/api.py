@@ -71,6 +71,18 @@ def _ecdsa_args(what, sigs, msghashes, pubkeys, sig_format, pk_format):
     return sigs, off, msghashes, pubkeys, n
 
 
+def _adaptor_args(what, adaptor_sigs, pubkeys, msgs32, enckeys, pk_format):
+    """shape checks shared by Engine.ecdsa_adaptor_verify_batch and Group.ecdsa_adaptor_verify_batch"""
+    if pk_format not in _ECDSA_PK_BYTES:
+        raise ValueError(f"{what}: pk_format must be 0, 1 or 2")
+    if adaptor_sigs is None or pubkeys is None or msgs32 is None or enckeys is None:
+        raise ValueError(f"{what}: missing array")
+    adaptor_sigs = _u8(adaptor_sigs); pubkeys = _u8(pubkeys); msgs32 = _u8(msgs32); enckeys = _u8(enckeys); n = adaptor_sigs.size // 162
+    _need(what + " adaptor_sigs", adaptor_sigs, 162 * n); _need(what + " msgs32", msgs32, 32 * n)
+    _need(what + " pubkeys", pubkeys, _ECDSA_PK_BYTES[pk_format] * n); _need(what + " enckeys", enckeys, _ECDSA_PK_BYTES[pk_format] * n)
+    return adaptor_sigs, pubkeys, msgs32, enckeys, n
+
+
 _TWEAK_KEY_BYTES = {0: 32, 1: 64, 2: 33}     # serialised x-only / secp256k1_xonly_pubkey or secp256k1_pubkey object / compressed
 
 
@@ -169,6 +181,25 @@ class Engine:
         self._check(self._lib.s2k_ecmult_batch_dev(self._h, stream, _dp(r_xy), _dp(r_inf), _dp(a_xy), _dp(a_inf), _dp(na), _dp(ng), n),
                     "s2k_ecmult_batch_dev")
 
+    def ecmult2_batch(self, a_xy, na, b_xy, nb, a_inf=None, b_inf=None):
+        """r[i] = na[i]*A[i] + nb[i]*B[i] (s2k_ecmult2_batch: two variable points, one chain of doublings); returns (n x 64 bytes, n flags)"""
+        if a_xy is None or na is None or b_xy is None or nb is None:
+            raise ValueError("ecmult2_batch: missing array")
+        a_xy = _u8(a_xy); b_xy = _u8(b_xy); na = _u8(na); nb = _u8(nb); n = a_xy.size // 64
+        a_inf = None if a_inf is None else _u8(a_inf); b_inf = None if b_inf is None else _u8(b_inf)
+        _need("ecmult2_batch a_xy", a_xy, 64 * n); _need("ecmult2_batch b_xy", b_xy, 64 * n)
+        _need("ecmult2_batch na", na, 32 * n); _need("ecmult2_batch nb", nb, 32 * n)
+        if a_inf is not None: _need("ecmult2_batch a_inf", a_inf, n)
+        if b_inf is not None: _need("ecmult2_batch b_inf", b_inf, n)
+        r = np.zeros((n, 64), np.uint8); inf = np.zeros(n, np.int32)
+        self._check(self._lib.s2k_ecmult2_batch(self._h, _p(r), _p(inf), _p(a_xy), _p(a_inf), _p(na), _p(b_xy), _p(b_inf), _p(nb), n), "s2k_ecmult2_batch")
+        return r, inf
+
+    def ecmult2_batch_dev(self, r_xy, r_inf, a_xy, na, b_xy, nb, a_inf=None, b_inf=None, stream=None):
+        n = a_xy.numel() // 64
+        self._check(self._lib.s2k_ecmult2_batch_dev(self._h, stream, _dp(r_xy), _dp(r_inf), _dp(a_xy), _dp(a_inf), _dp(na), _dp(b_xy), _dp(b_inf), _dp(nb), n),
+                    "s2k_ecmult2_batch_dev")
+
     # ---- secp256k1_ecmult_multi_var (src/ecmult.h:62) ----------------------------------------------------------
     def ecmult_multi(self, sc, pt_xy, g_sc=None, pt_inf=None):
         sc = _u8(sc); pt_xy = _u8(pt_xy); n = sc.size // 32
@@ -261,6 +292,21 @@ class Engine:
         n = sigs64.numel() // 64 if n is None else n
         self._check(self._lib.secp256k1_ecdsa_recover_batch_dev(self._h, stream, _dp(results), _dp(pubkeys_out64), _dp(sigs64), _dp(recids), _dp(msghashes), n),
                     "secp256k1_ecdsa_recover_batch_dev")
+
+    # ---- secp256k1_ecdsa_adaptor_verify (modules/ecdsa_adaptor/main_impl.h:236-282), batched ----
+    def ecdsa_adaptor_verify_batch(self, adaptor_sigs, pubkeys, msgs32, enckeys, pk_format=0):
+        """adaptor_sigs n*162; pubkeys and enckeys in one pk_format (0: n*33 compressed, 1: n*64 secp256k1_pubkey objects, 2: n*65); msgs32 n*32"""
+        adaptor_sigs, pubkeys, msgs32, enckeys, n = _adaptor_args("ecdsa_adaptor_verify_batch", adaptor_sigs, pubkeys, msgs32, enckeys, pk_format)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_ecdsa_adaptor_verify_batch(self._h, _p(res), _p(adaptor_sigs), _p(pubkeys), _p(msgs32), _p(enckeys), pk_format, n),
+                    "secp256k1_ecdsa_adaptor_verify_batch")
+        return res
+
+    def ecdsa_adaptor_verify_batch_dev(self, results, adaptor_sigs, pubkeys, msgs32, enckeys, pk_format=0, n=None, stream=None):
+        """every array in HBM (torch tensors)"""
+        n = adaptor_sigs.numel() // 162 if n is None else n
+        self._check(self._lib.secp256k1_ecdsa_adaptor_verify_batch_dev(self._h, stream, _dp(results), _dp(adaptor_sigs), _dp(pubkeys), _dp(msgs32), _dp(enckeys),
+                                                                       pk_format, n), "secp256k1_ecdsa_adaptor_verify_batch_dev")
 
     # ---- secp256k1_xonly_pubkey_tweak_add_check / _tweak_add (modules/extrakeys/main_impl.h:118-154) and secp256k1_ec_pubkey_tweak_add (secp256k1.c:766-790), batched ----
     def xonly_tweak_add_check_batch(self, tweaked32, parities, internal_keys, tweaks32, key_format=0):
@@ -653,6 +699,13 @@ class Group:
         res = np.zeros(n, np.int32)
         self._check(self._lib.secp256k1_ecdsa_verify_batch_group(self._h, _p(res), _p(sigs), _p(off), sig_format, _p(msghashes), _p(pubkeys), pk_format, n),
                     "secp256k1_ecdsa_verify_batch_group")
+        return res
+
+    def ecdsa_adaptor_verify_batch(self, adaptor_sigs, pubkeys, msgs32, enckeys, pk_format=0):
+        adaptor_sigs, pubkeys, msgs32, enckeys, n = _adaptor_args("ecdsa_adaptor_verify_batch_group", adaptor_sigs, pubkeys, msgs32, enckeys, pk_format)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_ecdsa_adaptor_verify_batch_group(self._h, _p(res), _p(adaptor_sigs), _p(pubkeys), _p(msgs32), _p(enckeys), pk_format, n),
+                    "secp256k1_ecdsa_adaptor_verify_batch_group")
         return res
 
     def xonly_tweak_add_check_batch(self, tweaked32, parities, internal_keys, tweaks32, key_format=0):

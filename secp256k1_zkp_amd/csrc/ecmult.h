@@ -835,3 +835,143 @@ S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scal
 #endif
     return 1;
 }
+
+
+// ---- the joint form: two variable points, no generator  R = na*A + nb*B ----------------------------------------------------------------
+// (the DLEQ half of an adaptor signature needs s*Y - e*R, adaptor.h; the reference takes two secp256k1_ecmult calls and a gej_add_var for it,
+// src/modules/ecdsa_adaptor/dleq_impl.h:146-150: 256 doublings and 132 table additions.)  Both points get a table of odd multiples, the two
+// tables are rescaled to ONE common Z exactly as in ecmult_lane_split (the second table slot of the lane's slice), and the GLV halves of na
+// (on A) and of nb (on B) run as four digit streams of 33 signed odd 4-bit digits, the top one fixed: 128 doublings and 132 additions, the
+// first of which just takes its operand.  Digit stream in LDS: words 0..15 = nibble (pos * 4 + stream), streams 0, 1 = the halves of na,
+// 2, 3 = those of nb.  Only the lock-step form exists: the function returns 0 without having produced anything when the wavefront is not
+// uniform (a lane with A.inf, B.inf or a zero scalar), when a lane meets an operand with the accumulator's own x coordinate, or when the
+// two tables cannot share a Z (a Z of zero: only points off the curve get there); the caller then runs ecmult_lane2_calls below.
+#define S2K_JOINT_ADDS (4 * 33)
+S2K_HD int ecmult_lane2(gej& R, const gej& A, const scalar& na, const gej& B, const scalar& nb, const lane_mem& lm) {
+    u32* const ptab = lm.ptab; const s2k_lds_ptr dig = lm.dig;
+    const int active = (!A.inf) & (!B.inf) & (!sc_is_zero(na)) & (!sc_is_zero(nb));
+    if (!S2K_WAVE_ALL(active)) return 0;
+    u32 sneg = 0;                                                    // bit st: stream st is negative
+    S2K_PROF_DECL;
+    {
+        u32 dw[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++) dw[i] = 0;
+        auto put = [&](const half_scalar& h, const int st) {             // the 32 digits of one stream into their nibbles (st a constant)
+            sneg |= (u32)h.neg << st;
+#pragma unroll
+            for (int pos = 0; pos < 32; pos++) {                         // pos 0 = digit 31 (most significant after the fixed top digit)
+                const int i = 31 - pos, bit = 4 * i + 1, word = bit >> 5, sh = bit & 31;
+                const u64 pair = (u64)h.w[word] | ((u64)h.w[word + 1] << 32);      // (word <= 3)
+                const u32 v = (u32)(pair >> sh) & 15u;
+                const int nib = pos * 4 + st;
+                dw[nib >> 3] |= v << ((nib & 7) * 4);
+            }
+        };
+        { half_scalar h0, h1; sc_split_lambda_odd(h0, h1, na); put(h0, 0); put(h1, 1); }
+        { half_scalar h0, h1; sc_split_lambda_odd(h0, h1, nb); put(h0, 2); put(h1, 3); }
+#pragma unroll
+        for (int i = 0; i < 16; i++) dig[i * S2K_DIG_STRIDE] = dw[i];
+        fe za, zb, ziso;
+        S2K_PROF_MARK(1);
+        ptab_build_raw(za, ptab, A);
+        ptab_build_raw(zb, ptab + S2K_PTAB_TABLE_WORDS, B);
+        fe_mul(ziso, za, zb);
+        if (S2K_WAVE_ANY(fe_normalizes_to_zero(ziso))) return 0;
+        S2K_PROF_MARK(8);
+        ptab_rescale(ptab, &zb);
+        ptab_rescale(ptab + S2K_PTAB_TABLE_WORDS, &za);
+        S2K_PROF_MARK(9);
+#pragma unroll
+        for (int i = 0; i < 9; i++) ptab[S2K_PTAB_ZISO + i] = ziso.n[i];
+    }
+    auto op_locate = [&](const u32*& addr, int& neg, int idx) {
+        const int st = idx & 3;
+        u32 v = 8u;                                                                     // the fixed top digit +1
+        if (idx >= 4 && idx < S2K_JOINT_ADDS) { const int nib = idx - 4; v = (dig[(nib >> 3) * S2K_DIG_STRIDE] >> ((nib & 7) * 4)) & 15u; }
+        neg = (v < 8u) ^ (int)((sneg >> st) & 1u);
+        const u32 e = (v < 8u) ? (7u - v) : (v - 8u);
+        addr = ptab + (st >> 1) * S2K_PTAB_TABLE_WORDS + e * S2K_PTAB_ENTRY_WORDS + (((st & 1) && S2K_PTAB_TWINS) ? 16 : 0);
+    };
+    auto op_decode = [&](ge& o, const u32 raw[16], int neg, int lam) {
+        fe y, yn;
+        fe_from_words(o.x, raw); fe_from_words(y, raw + 8);
+        if (lam) { fe beta; fe_set_beta(beta); fe_mul(o.x, o.x, beta); }          // `lam` is a compile-time constant at every call site
+        fe_neg(yn, y, 1);
+        fe_select(o.y, yn, y, neg);
+    };
+    const u32* nxt_addr; int nxt_neg;
+    u32 raw[16];
+    ge cur;
+    op_locate(nxt_addr, nxt_neg, 0);
+#pragma unroll
+    for (int k = 0; k < 16; k++) raw[k] = nxt_addr[k];
+    op_decode(cur, raw, nxt_neg, 0);
+    op_locate(nxt_addr, nxt_neg, 1);
+    // additions 0..131 as 66 (plain stream, lambda stream) pairs, as in ecmult_lane_split; 4 doublings in front of every group of four
+    // but the first.  In place: a lane that meets its own x coordinate makes the caller start over.  (Past the last addition op_locate
+    // wraps to the fixed top digit: a request for a record of the lane's own table that nobody decodes.)
+    int au = 0;
+    while (au < S2K_JOINT_ADDS) {
+        if (au >= 4 && !(au & 3)) {
+#pragma unroll 1
+            for (int k = 0; k < 4; k++) gej_double_lean(R, R);
+            S2K_PROF_MARK(6);
+        }
+#pragma unroll
+        for (int k = 0; k < 16; k++) raw[k] = nxt_addr[k];                  // request the next record before the arithmetic
+        if (au == 0) gej_set_ge(R, cur);
+        else { const int same_x = gej_add_ge_lean(R, R, cur); if (S2K_WAVE_ANY(same_x)) return 0; }
+        op_decode(cur, raw, nxt_neg, !S2K_PTAB_TWINS);                      // operand of the lambda stream
+        op_locate(nxt_addr, nxt_neg, au + 2);
+#pragma unroll
+        for (int k = 0; k < 16; k++) raw[k] = nxt_addr[k];
+        { const int same_x = gej_add_ge_lean(R, R, cur); if (S2K_WAVE_ANY(same_x)) return 0; }
+        au += 2;
+        op_decode(cur, raw, nxt_neg, 0);
+        op_locate(nxt_addr, nxt_neg, au + 1);
+    }
+    { fe zi; ptab_load_ziso(zi, ptab); fe_mul(R.z, R.z, zi); }             // back to the real curve
+    S2K_PROF_MARK(10);
+#ifdef S2K_ON_JOINT_DONE
+    S2K_ON_JOINT_DONE();                                                                      // host test build: count completed joint runs
+#endif
+    return 1;
+}
+
+// A Jacobian point parked in memory between two multiplications, so that it is not held in registers across one: 28 words, `stride`
+// words apart (the kernels interleave the lanes of a launch: word k of every lane side by side).
+#define S2K_PARK_GEJ_WORDS 28
+S2K_HD void gej_park(u32* p, size_t stride, const gej& a) {
+    fe x = a.x, y = a.y, z = a.z;
+    fe_norm_weak(x); fe_norm_weak(y); fe_norm_weak(z);
+#pragma unroll
+    for (int i = 0; i < 9; i++) { p[i * stride] = x.n[i]; p[(9 + i) * stride] = y.n[i]; p[(18 + i) * stride] = z.n[i]; }
+    p[27 * stride] = (u32)a.inf;
+}
+S2K_HD void gej_unpark(gej& a, const u32* p, size_t stride) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) { a.x.n[i] = p[i * stride]; a.y.n[i] = p[(9 + i) * stride]; a.z.n[i] = p[(18 + i) * stride]; }
+    a.inf = (int)p[27 * stride];
+}
+// The same sum as the reference takes it: two ecmult_lane calls and a gej_add_var (every input is served: infinity, zero scalars, A = +-B).
+// The first product waits in `park` (S2K_PARK_GEJ_WORDS words of this lane) while the second is computed.
+// load(k, P, n) hands in term k (0: A and na, 1: B and nb) when it is needed, so that a kernel can read its inputs again from global
+// memory instead of holding the second term in registers across the first multiplication.
+template <class Load>
+S2K_HD void ecmult_lane2_calls(gej& R, Load load, const u32* gtab, const lane_mem& lm, u32* park, size_t park_stride) {
+    scalar zero; sc_set_zero(zero);
+    {
+        gej P, T; scalar n;
+        load(0, P, n);
+        ecmult_lane(T, P, n, zero, 0, gtab, lm);
+        gej_park(park, park_stride, T);
+    }
+    gej P, T, F; scalar n;
+    load(1, P, n);
+    ecmult_lane(T, P, n, zero, 0, gtab, lm);
+    gej_unpark(F, park, park_stride);
+    gej_add_var(R, F, T);
+}
+// An offset of zero the compiler cannot see through: inputs read again through it are loaded again, not kept from the first time.
+S2K_HD u32 s2k_opaque_zero() { u32 z = 0; S2K_CHAIN(z); return z; }

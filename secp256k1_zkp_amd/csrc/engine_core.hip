@@ -790,6 +790,18 @@ extern "C" int secp256k1_ecdsa_verify_amd(const void* ctx, const void* sig, cons
     if (!secp256k1_ecdsa_verify_batch(e, &res, (const unsigned char*)sig, nullptr, 1, msghash32, (const unsigned char*)pubkey, 1, 1)) return 0;
     return res;
 }
+// include/secp256k1_ecdsa_adaptor.h (src/modules/ecdsa_adaptor/main_impl.h:236) -- pubkey and enckey point at 64-byte secp256k1_pubkey
+// objects (the kernel lives in engine_adaptor.hip)
+extern "C" int secp256k1_ecdsa_adaptor_verify_amd(const void* ctx, const unsigned char* adaptor_sig162, const void* pubkey, const unsigned char* msg32, const void* enckey) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!adaptor_sig162 || !pubkey || !msg32 || !enckey) return s2k_fail_arg("secp256k1_ecdsa_adaptor_verify_amd", "illegal argument (ARG_CHECK)");
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0;
+    if (!secp256k1_ecdsa_adaptor_verify_batch(e, &res, adaptor_sig162, (const unsigned char*)pubkey, msg32, (const unsigned char*)enckey, 1, 1)) return 0;
+    return res;
+}
 // include/secp256k1_recovery.h:112 -- signature points at the 65-byte secp256k1_ecdsa_recoverable_signature object: the little-endian
 // limbs of r and s, then the recovery id (src/modules/recovery/main_impl.h:13-36); pubkey receives a secp256k1_pubkey object
 extern "C" int secp256k1_ecdsa_recover_amd(const void* ctx, void* pubkey, const void* signature, const unsigned char* msghash32) {
@@ -1226,6 +1238,29 @@ extern "C" int secp256k1_ecdsa_verify_batch_group(s2k_group* g, int32_t* results
             if (hi == lo) return 1;
             return secp256k1_ecdsa_verify_batch(e, results + lo, der ? sigs : sigs + 64 * lo, der ? sig_off + lo : nullptr, sig_format, msghash32 + 32 * lo,
                                                 pubkeys + pkb * lo, pk_format, hi - lo);
+        };
+    }
+    const int ok = group_run(g, jobs);
+    if (!ok) memset(results, 0, sizeof(int32_t) * n);
+    return ok;
+}
+extern "C" int secp256k1_ecdsa_adaptor_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* adaptor_sigs162, const unsigned char* pubkeys,
+                                                          const unsigned char* msgs32, const unsigned char* enckeys, int pk_format, size_t n) {
+    const char* who = "secp256k1_ecdsa_adaptor_verify_batch_group";
+    if (!g || g->eng.empty()) return s2k_fail(who, "null group");
+    if (n == 0) return 1;
+    if (!results || !adaptor_sigs162 || !pubkeys || !msgs32 || !enckeys) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    if (pk_format < 0 || pk_format > 2) return s2k_fail_arg(who, "pk_format must be 0 (compressed), 1 (object) or 2 (uncompressed / hybrid)");
+    std::lock_guard<std::mutex> call(g->call_mu);
+    memset(results, 0, sizeof(int32_t) * n);
+    const size_t k = g->eng.size(), pkb = pk_format == 0 ? 33 : pk_format == 1 ? 64 : 65;
+    std::vector<std::function<int()>> jobs(k);
+    for (size_t i = 0; i < k; i++) {
+        size_t lo, hi; group_share(n, k, i, lo, hi);
+        s2k_engine* e = g->eng[i];
+        jobs[i] = [=]() -> int {
+            if (hi == lo) return 1;
+            return secp256k1_ecdsa_adaptor_verify_batch(e, results + lo, adaptor_sigs162 + 162 * lo, pubkeys + pkb * lo, msgs32 + 32 * lo, enckeys + pkb * lo, pk_format, hi - lo);
         };
     }
     const int ok = group_run(g, jobs);

@@ -1,7 +1,7 @@
 // engine_internal.h -- what the translation units of the gfx950 batch-verification engine share (see include/secp256k1_zkp_amd.h):
 // the engine object, the per-device table pool, error plumbing, workspace carving and the host functions one kernel family offers the others.
 //
-// The library is ten translation units, one per kernel family, compiled separately (hipcc --offload-arch=gfx950 -O3 -fPIC -c) and linked
+// The library is eleven translation units, one per kernel family, compiled separately (hipcc --offload-arch=gfx950 -O3 -fPIC -c) and linked
 // into one shared object (see __graft_entry__.build):
 //   engine_core.hip        table construction, the per-device pool and generator-table cache, engine lifecycle / options / groups,
 //                          s2k_ecmult_batch, BIP-340, the single-item `_amd` forms and the `_group` forms of every family
@@ -14,6 +14,7 @@
 //   engine_whitelist.hip   whitelist-signature verification (whitelist.h)
 //   engine_tweak.hip       Taproot tweak checks and public-key tweak-add (tweak.h)
 //   engine_generator.hip   asset generators (generate, parse, serialize) and Pedersen commitments to public amounts (generator.h)
+//   engine_adaptor.hip     ECDSA adaptor-signature verification (adaptor.h) and the two-point multiplication s2k_ecmult2_batch
 // The per-lane arithmetic lives in the headers next to these files.  No device function is called across translation units (no -fgpu-rdc):
 // a family that needs another family's kernels calls the HOST function that launches them.
 // There is no CPU implementation behind the entry points: without a HIP device every call fails loudly.
