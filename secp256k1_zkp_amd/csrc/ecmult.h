@@ -654,27 +654,61 @@ S2K_HD int ecmult_lane_split(gej& R, const gej& A, const gej& T, const scalar& n
 // (secp256k1_rangeproof_pub_expand, rangeproof_impl.h:19-51), so   e_j*P_j = e_j*C + f_j*H ,  f_j = -(j 4^i 10^exp) e_j mod n :
 // the variable point is the same for all four steps of the ring, and the part that changes goes through a fixed-base table of H laid
 // out exactly like the one of G (gtable.h; the engine keeps a small cache of them keyed by the generator's 64 bytes).  What that buys:
-//   * the two odd-multiples tables (of C and of T = 2^64*C) and the 64-doubling chain are built ONCE per ring instead of once per step,
-//     so they can be twice as large: signed odd 5-bit digits, 16 entries per table, 13 additions per stream instead of 17.
-//     (13, not 14: 13 digits d_i = 2 b_i - 31 represent every odd k with |k| < 2^65 -- sum d_i 32^i = 2B - (2^65 - 1), so b is read off
-//     B = (k - 1)/2 + 2^64: bit t of B is bit t + 1 of k and bit 64 is set, i.e. the top digit is 16 | (k >> 61) -- and the four 65-bit
-//     pieces of sc_split_pieces are odd and below 2^65.  ecmult_lane_split's 4-bit digits need a fixed 17th digit because 16 of them
-//     only reach 2^64.)  So a step is 12 x 5 doublings and 52 additions, the first of which just takes its operand;
+//   * the table of the variable point and the 64-doubling chain to T = 2^64*C are built ONCE per ring instead of once per step, so the
+//     table can be twice as large as ecmult_lane_split's two: 32 sectors of 64 bytes;
 //   * no "key <- key + B", "T <- T + 2^64*B" updates between the steps;
 //   * + W (the table's number of windows) additions from H's table on the steps with j > 0.
-// Per ring: 1 chain + 2 tables + 4 x (60 doublings + 52 additions) + 77 table additions, against 4 x (64 doublings + 68 + 11 additions
+// The joint form (S2K_RING_JOINT = 1, the default): ONE table indexed by the digits of BOTH bases.  Its 32 sectors hold
+//     J(a, b) = a*C + b*T ,  a in {1, 3, 5, 7},  b in {+-1, +-3, +-5, +-7} ,  at sector ((a - 1) / 2) * 8 + (b + 7) / 2 ,
+// all on one Z, and a plain operand carries the digit of the C piece and the digit of the T piece of a GLV half at once (the lambda
+// operand is the same entry with beta on x).  The four 65-bit pieces of sc_split_pieces are odd and below 2^65; each is cut into 22 signed
+// odd 3-bit digits d_i = 2 b_i - 7, and 22 of them need no fixed top digit: sum d_i 8^i = 2B - (2^66 - 1), so b is read off
+// B = (k - 1)/2 + 2^65 -- bit t of B is bit t + 1 of k, bit 64 is clear and bit 65 set, i.e. the top field is 4 | bit 63 of B.  With the
+// pieces' signs folded in, level i of a half has the signed digits (dC, dT) and takes  sign(dC) * J(|dC|, sign(dC) dT) : an entry index and
+// ONE negation flag (ring_joint_field), six bits.
+// A step is 22 levels (3 doublings in front of every level but the first; plain operand, lambda operand): 63 doublings and 44 additions,
+// the first of which just takes its operand, and 22 beta products.
+// Per ring: 1 chain + the table + 4 x (63 doublings + 44 additions) + 77 table additions, against 4 x (64 doublings + 68 + 11 additions
 // + 2 tables + a chain quarter + 2 key updates) for ecmult_lane_split.
+// Construction (ecmult_ring_tables): two 4-entry chains of odd multiples (ptab_build_raw_n<4>), both rescaled to one Z; 16 conjugate
+// additions (aC + bT and aC - bT together: Z = dx for both, 5M + 3S the pair); then every pair is brought to the product of all sixteen dx
+// by prefix / suffix products.  370 products + squarings per ring.  No addition in it can be exceptional for a finite C (a*C = +-b*T would
+// need n | a -+ b 2^64: odd, nonzero, below n); a dx of zero would all the same end up as a factor of the Z factor, and a step that finds
+// the Z factor zero returns 0 like one that met an exceptional addition.
 // Lane memory: `rtab`, S2K_RTAB_WORDS words of HBM: 32 finished 64-byte sectors back to back (2 KB: all the main loop touches) and the Z
-// factor; the parked entries of the construction live in a per-wavefront, lane-interleaved area (S2K_RRAW_WAVE_WORDS).
-// Digit stream in LDS (S2K_RING_DIG_WORDS words per lane): words 0..8 = 5-bit digit (pos * 4 + stream), six per word; 9..17 = s and 18..26 = f,
-// both recoded for the signed fixed-base windows (gtab_recode).
+// factor; the parked entries of the construction live in a per-wavefront, lane-interleaved area (S2K_RRAW_WAVE_WORDS).  A lane's 32 x 27
+// words of it (word w at raw[w * S2K_RAW_WS]) during the construction:
+//     words   0..143  the eight rescaled chain entries, 18 words (x, y) each: 0..3 = C, 3C, 5C, 7C; 4..7 = T, 3T, 5T, 7T
+//     words 144..863  pair k = 4 * ((a - 1) / 2) + (b - 1) / 2 : 45 words (x+, y+, x-, y-, product of the dx before it)
+//     (slots 24..31, i.e. words 648..863, first hold the two chains as ptab_build_raw_n parks them; they are dead before pair 11 is written)
+// Digit stream in LDS (S2K_RING_DIG_WORDS words per lane): words 0..8 = six-bit field (level * 2 + half), five per word; 9..17 = s and
+// 18..26 = f, both recoded for the signed fixed-base windows (gtab_recode).
 // Only the lock-step form exists (every lane of the wavefront works: the caller gives idle lanes a dummy point and dummy scalars);
 // ecmult_ring_step returns 0, having produced nothing, when a lane met an operand with its own x coordinate, and the caller then takes
 // that step through ecmult_lane on P_j itself.
+//
+// The separate form (S2K_RING_JOINT = 0: what the joint form replaced, kept for A/B runs and as the control of the host tests): two
+// 16-entry tables of odd multiples, of C and of T, one operand per piece.  Signed odd 5-bit digits, 13 additions per stream
+// (13, not 14: 13 digits d_i = 2 b_i - 31 represent every odd k with |k| < 2^65 -- sum d_i 32^i = 2B - (2^65 - 1), so b is read off
+// B = (k - 1)/2 + 2^64: bit t of B is bit t + 1 of k and bit 64 is set, i.e. the top digit is 16 | (k >> 61).  ecmult_lane_split's 4-bit
+// digits need a fixed 17th digit because 16 of them only reach 2^64.)  So a step is 12 x 5 doublings, 52 additions and 26 beta products;
+// the construction is two chains of one doubling + 15 co-Z additions and 32 rescales, 385 products + squarings per ring.  Digit words
+// 0..8 = 5-bit digit (pos * 4 + stream), six per word.
+#ifndef S2K_RING_JOINT
+#define S2K_RING_JOINT 1
+#endif
+#if S2K_RING_JOINT
+#define S2K_RING_W 3
+#define S2K_RING_DIGITS 22                                      /* 22 signed odd 3-bit digits: every odd |k| < 2^66, no extra top digit */
+#define S2K_RING_ADDS_P (2 * S2K_RING_DIGITS)                   /* one operand per level and GLV half */
+#define S2K_RING_GROUP 2                                        /* additions between two runs of doublings */
+#else
 #define S2K_RING_W 5
-#define S2K_RING_ENTRIES 16
 #define S2K_RING_DIGITS 13                                      /* 13 signed odd 5-bit digits: every odd |k| < 2^65, no extra top digit (below) */
 #define S2K_RING_ADDS_P (4 * S2K_RING_DIGITS)
+#define S2K_RING_GROUP 4
+#endif
+#define S2K_RING_ENTRIES 16                                     /* (per table in the separate form; the joint table has 2 x 16 sectors) */
 #define S2K_RING_DIG_WORDS 27
 #define S2K_RTAB_TABLE_WORDS (S2K_RING_ENTRIES * 16)
 #define S2K_RTAB_ZISO (2 * S2K_RTAB_TABLE_WORDS)
@@ -688,7 +722,129 @@ S2K_HD int ecmult_lane_split(gej& R, const gej& A, const gej& T, const scalar& n
 #define S2K_RAW_ES (27 * S2K_RAW_WS)
 #define S2K_RRAW_WAVE_WORDS (2 * S2K_RING_ENTRIES * 27 * 64)
 
+#if S2K_RING_JOINT
+// word w .. w + 8 of this lane's column of the parking area
+S2K_HD void rraw_store(u32* raw, int w, const fe& a) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        if (S2K_NT_PARK && S2K_RAW_WS > 1) S2K_ST_NT(a.n[i], &raw[(w + i) * S2K_RAW_WS]);
+        else raw[(w + i) * S2K_RAW_WS] = a.n[i];
+    }
+}
+S2K_HD void rraw_load(fe& a, const u32* raw, int w) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) a.n[i] = (S2K_NT_PARK && S2K_RAW_WS > 1) ? S2K_LD_NT(&raw[(w + i) * S2K_RAW_WS]) : raw[(w + i) * S2K_RAW_WS];
+}
+#define S2K_RJ_CHAIN_SLOT 24                                    /* the two raw chains: slots 24..27 (C) and 28..31 (T) of the parking area */
+#define S2K_RJ_PAIR0 144                                        /* first word of pair 0 */
+#define S2K_RJ_PAIR_WORDS 45
+// the 3-bit field b_i (digit d_i = 2 b_i - 7, i = 0 least significant) of an odd piece below 2^65
+S2K_HD u32 ring_piece_field(const piece65& p, int i) {
+    const int bit = S2K_RING_W * i + 1, word = bit >> 5, sh = bit & 31;
+    const u64 pair = (u64)p.w[word] | ((u64)(word + 1 < 3 ? p.w[word + 1] : 0u) << 32);
+    u32 v = (u32)(pair >> sh) & 7u;
+    if (i == S2K_RING_DIGITS - 1) v |= 4u;                      // bit 65 of B (the piece is below 2^65: bits 65, 66 of it are clear)
+    return v;
+}
+// fields vc, vt of the C piece and the T piece at one level, sc, st the pieces' signs (1 = negative)  ->  neg << 5 | sector: the operand is
+// sign(dC) * J(|dC|, sign(dC) * dT) with dC = +-(2 vc - 7), dT = +-(2 vt - 7)
+S2K_HD u32 ring_joint_field(u32 vc, u32 vt, u32 sc, u32 st) {
+    const u32 neg = (u32)(vc < 4u) ^ sc;
+    const u32 ai = vc < 4u ? 3u - vc : vc - 4u;                 // (|dC| - 1) / 2
+    const u32 bi = vt ^ ((neg ^ st) ? 7u : 0u);                 // (b + 7) / 2 ; negating b = 2 vt - 7 is vt -> 7 - vt
+    return (neg << 5) | (ai << 3) | bi;
+}
+// the digit words 0..8 of a step: field (level * 2 + half), level 0 = most significant, five six-bit fields per word
+S2K_HD void ring_joint_recode(u32 dw[9], const piece65 pc[4]) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) dw[i] = 0;
+#pragma unroll
+    for (int hf = 0; hf < 2; hf++) {
+#pragma unroll
+        for (int pos = 0; pos < S2K_RING_DIGITS; pos++) {
+            const int i = S2K_RING_DIGITS - 1 - pos, idx = pos * 2 + hf;
+            const u32 v = ring_joint_field(ring_piece_field(pc[hf], i), ring_piece_field(pc[2 + hf], i), (u32)pc[hf].neg, (u32)pc[2 + hf].neg);
+            dw[idx / 5] |= v << ((idx % 5) * 6);
+        }
+    }
+}
 // C, T = 2^64*C finite, magnitudes <= (5,3,1).  rtab: this lane's S2K_RTAB_WORDS; raw: this lane's column of its wavefront's parking area
+S2K_HD void ecmult_ring_tables(u32* rtab, u32* raw, const gej& C, const gej& T) {
+    {   // the chains, both on the Z  za * zt  (which waits in the Z factor's place)
+        fe za, zt, zs;
+        ptab_build_raw_n<4, S2K_RAW_WS, S2K_RAW_ES>(za, raw + S2K_RJ_CHAIN_SLOT * S2K_RAW_ES, C);
+        ptab_build_raw_n<4, S2K_RAW_WS, S2K_RAW_ES>(zt, raw + (S2K_RJ_CHAIN_SLOT + 4) * S2K_RAW_ES, T);
+#pragma unroll 1
+        for (int e = 7; e >= 0; e--) {
+            if ((e & 3) == 3) zs = (e >> 2) ? za : zt;          // each chain by the OTHER one's Z
+            fe x, y, h, zs2, zs3;
+            rraw_load(x, raw, (S2K_RJ_CHAIN_SLOT + e) * 27); rraw_load(y, raw, (S2K_RJ_CHAIN_SLOT + e) * 27 + 9); rraw_load(h, raw, (S2K_RJ_CHAIN_SLOT + e) * 27 + 18);
+            fe_sqr(zs2, zs); fe_mul(zs3, zs2, zs);
+            fe_mul2(x, x, zs2, y, y, zs3);
+            rraw_store(raw, 18 * e, x); rraw_store(raw, 18 * e + 9, y);
+            fe_mul(zs, zs, h);                                  // ratio z_i / z_{i-1} joins the running product for the entries below
+        }
+        fe_mul(zs, za, zt);
+#pragma unroll
+        for (int i = 0; i < 9; i++) rtab[S2K_RTAB_ZISO + i] = zs.n[i];
+    }
+    {   // the pairs: P1 = aC, P2 = bT as affine points of the chains' curve; P1 + P2 and P1 - P2 both come out with Z = dx = x2 - x1
+        fe p; fe_set_int(p, 1);
+#pragma unroll 1
+        for (int k = 0; k < 16; k++) {
+            const int w1o = 18 * (k >> 2), w2o = 18 * (4 + (k & 3)), rec = S2K_RJ_PAIR0 + S2K_RJ_PAIR_WORDS * k;
+            fe x1, y1, x2, y2;
+            rraw_load(x1, raw, w1o); rraw_load(y1, raw, w1o + 9); rraw_load(x2, raw, w2o); rraw_load(y2, raw, w2o + 9);
+            fe dx, dy, sy, t, c, d, d2, w1, w2, e, a1, x3, x3m, y3, y3m;
+            fe_neg(t, x1, 1); fe_add2(dx, x2, t); fe_norm_weak(dx);
+            fe_neg(t, y1, 1); fe_add2(dy, y2, t); fe_norm_weak(dy);
+            fe_add2(sy, y1, y2); fe_norm_weak(sy);
+            fe_sqr2(c, dx, d, dy);
+            fe_mul2(w1, x1, c, w2, x2, c);
+            fe_neg(e, w1, 1); fe_add(e, w2);                                  // dx^3                        (3)
+            fe_mul_sqr(a1, y1, e, d2, sy);                                    // (1*3)
+            fe_add2(t, w1, w2); fe_neg(t, t, 2);                              // -(W1 + W2)                  (3)
+            fe_add2(x3, d, t); fe_add2(x3m, d2, t);                           // X(P1 + P2), X(P1 - P2)      (4)
+            fe_neg(t, x3, 4); fe_add(t, w1);                                  // W1 - X3                     (6)
+            fe_neg(e, w1, 1); fe_add(e, x3m);                                 // X3' - W1                    (6)
+            fe_mul2(y3, dy, t, y3m, sy, e);                                   // (1*6, 1*6)
+            fe_neg(t, a1, 1); fe_add(y3, t); fe_add(y3m, t);                  // Y = dy (W1 - X3) - y1 dx^3 ; Y' = sy (X3' - W1) - y1 dx^3   (3)
+            rraw_store(raw, rec, x3); rraw_store(raw, rec + 9, y3); rraw_store(raw, rec + 18, x3m); rraw_store(raw, rec + 27, y3m);
+            rraw_store(raw, rec + 36, p);
+            fe_mul(p, p, dx);
+        }
+    }
+    fe s; fe_set_int(s, 1);
+#pragma unroll 1
+    for (int k = 15; k >= 0; k--) {                              // pair k times (product of the other fifteen dx): every entry on Z = za zt prod dx
+        const int ai = k >> 2, bi = k & 3, rec = S2K_RJ_PAIR0 + S2K_RJ_PAIR_WORDS * k;
+        fe xp, yp, xm, ym, m, x1, dx;
+        rraw_load(xp, raw, rec); rraw_load(yp, raw, rec + 9); rraw_load(xm, raw, rec + 18); rraw_load(ym, raw, rec + 27); rraw_load(m, raw, rec + 36);
+        rraw_load(x1, raw, 18 * ai); rraw_load(dx, raw, 18 * (4 + bi));
+        fe_neg(x1, x1, 1); fe_add(dx, x1); fe_norm_weak(dx);
+        fe_mul2(m, m, s, s, s, dx);
+        fe m2, m3; fe_sqr(m2, m); fe_mul(m3, m2, m);
+        fe_mul2(xp, xp, m2, xm, xm, m2);                                      // (4*1)
+        fe_mul2(yp, yp, m3, ym, ym, m3);                                      // (3*1)
+        fe_normalize(xp); fe_normalize(yp); fe_normalize(xm); fe_normalize(ym);
+        u32* const ep = rtab + (ai * 8 + 4 + bi) * 16;                        // J(a, +b)
+        u32* const em = rtab + (ai * 8 + 3 - bi) * 16;                        // J(a, -b)
+        u32 wx[8], wy[8];
+        fe_to_words(wx, xp); fe_to_words(wy, yp);
+#pragma unroll
+        for (int i = 0; i < 8; i++) { ep[i] = wx[i]; ep[8 + i] = wy[i]; }
+        fe_to_words(wx, xm); fe_to_words(wy, ym);
+#pragma unroll
+        for (int i = 0; i < 8; i++) { em[i] = wx[i]; em[8 + i] = wy[i]; }
+    }
+    fe ziso;
+#pragma unroll
+    for (int i = 0; i < 9; i++) ziso.n[i] = rtab[S2K_RTAB_ZISO + i];
+    fe_mul(ziso, ziso, s);                                                    // (a dx of zero makes the Z factor zero: ecmult_ring_step then returns 0)
+#pragma unroll
+    for (int i = 0; i < 9; i++) rtab[S2K_RTAB_ZISO + i] = ziso.n[i];
+}
+#else
 S2K_HD void ecmult_ring_tables(u32* rtab, u32* raw, const gej& C, const gej& T) {
     fe za, zt, ziso;
     u32* const raw_t = raw + S2K_RING_ENTRIES * S2K_RAW_ES;
@@ -700,15 +856,21 @@ S2K_HD void ecmult_ring_tables(u32* rtab, u32* raw, const gej& C, const gej& T) 
 #pragma unroll
     for (int i = 0; i < 9; i++) rtab[S2K_RTAB_ZISO + i] = ziso.n[i];
 }
+#endif
 // e != 0; has_f uniform over the wavefront.  htab: this lane's generator's table (same layout as gtab).
 S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scalar& s, const scalar& f, int has_f, const u32* gtab, const u32* htab,
                             const s2k_lds_ptr dig) {
+#if !S2K_RING_JOINT
     u32 sneg = 0;
+#endif
     S2K_PROF_DECL;
     {
         half_scalar h0, h1; sc_split_lambda_odd(h0, h1, e);
         piece65 pc[4]; sc_split_pieces(pc, h0, h1);
         u32 dw[9];
+#if S2K_RING_JOINT
+        ring_joint_recode(dw, pc);
+#else
 #pragma unroll
         for (int i = 0; i < 9; i++) dw[i] = 0;
 #pragma unroll
@@ -724,6 +886,7 @@ S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scal
                 dw[nib / 6] |= v << ((nib % 6) * 5);
             }
         }
+#endif
 #pragma unroll
         for (int i = 0; i < 9; i++) dig[i * S2K_DIG_STRIDE] = dw[i];
         u32 sr[S2K_GTAB_SWORDS], fr[S2K_GTAB_SWORDS]; gtab_recode(sr, s.d, gtab); gtab_recode(fr, f.d, has_f ? htab : gtab);
@@ -737,12 +900,19 @@ S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scal
     auto op_locate = [&](const u32*& addr, int& valid, int& neg, int idx) {
         addr = rtab; valid = 0; neg = 0;
         if (idx < a_g0) {
+#if S2K_RING_JOINT
+            const u32 v = (dig[(idx / 5) * S2K_DIG_STRIDE] >> ((idx % 5) * 6)) & 63u;       // ring_joint_field
+            valid = 1;
+            neg = (int)(v >> 5);
+            addr = rtab + (v & 31u) * 16;
+#else
             const int st = idx & 3;
             const u32 v = (dig[(idx / 6) * S2K_DIG_STRIDE] >> ((idx % 6) * 5)) & 31u;
             valid = 1;
             neg = (v < 16u) ^ (int)((sneg >> st) & 1u);
             const u32 en = (v < 16u) ? (15u - v) : (v - 16u);
             addr = rtab + (st >> 1) * S2K_RTAB_TABLE_WORDS + en * 16;
+#endif
         } else if (idx < a_end) {
             const int second = idx >= a_h0;
             const int g = idx - (second ? a_h0 : a_g0), base = second ? 18 : 9, w = (int)(((u32)g * (second ? GH.D : GG.D)) >> 5);
@@ -764,10 +934,11 @@ S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scal
     for (int k = 0; k < 16; k++) raw[k] = nxt_addr[k];
     op_decode(cur, raw, nxt_neg, 0);
     op_locate(nxt_addr, nxt_valid, nxt_neg, 1);
-    // variable part: additions 0..51 as 26 (plain stream, lambda stream) pairs, 5 doublings in front of every group of four but the first
+    // variable part, separate form: additions 0..51 as 26 (plain stream, lambda stream) pairs, 5 doublings in front of every group of four
+    // but the first; joint form: additions 0..43 as 22 such pairs, one per level, 3 doublings in front of every pair but the first
     int au = 0;
     while (au < a_g0) {
-        if (au >= 4 && !(au & 3)) {
+        if (au >= S2K_RING_GROUP && !(au & (S2K_RING_GROUP - 1))) {
             S2K_PROF_MARK(7);
 #pragma unroll 1
             for (int k = 0; k < S2K_RING_W; k++) gej_double_lean(R, R);
@@ -792,6 +963,11 @@ S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scal
 #pragma unroll
         for (int i = 0; i < 9; i++) zi.n[i] = rtab[S2K_RTAB_ZISO + i];
         fe_mul(R.z, R.z, zi);
+        // a Z factor of zero (joint form: a table whose construction met a dx of zero) makes ZZ zero below, it stays zero through the table
+        // part, and the one ZZ test behind it sends the step back; only the form without that test needs one of its own
+#if S2K_RING_JOINT && !S2K_XYZZ_TABLE_PART
+        if (S2K_WAVE_ANY(fe_normalizes_to_zero(zi))) return 0;
+#endif
     }
     // table part (G, then H): a zero window adds nothing (per lane), so these additions are committed by select
 #if S2K_XYZZ_TABLE_PART

@@ -31,8 +31,8 @@ names = ["step prologue (key load, next key, T update)", "ecmult: split + digits
          "hash + bookkeeping", "main loop: 4 lean doublings", "main loop: lean addition + operand decode/locate", "split: 2 x co-Z table construction",
          "split: 2 x table rescale", "split: generator additions + leaving the isomorphic curve", "ring: 2^64 * key chain (64 doublings)"]
 if os.environ.get("S2K_GEN_CACHE", "") != "0":        # the shared-generator form of the kernel (rp_ring_shared / ecmult_ring_step) uses the slots like this
-    names = ["step prologue (scalars, f_j)", "ring step: split + digits", "-", "-", "to-affine (inversion)", "hash + bookkeeping", "ring step: 5 lean doublings",
-             "ring step: lean additions + operand decode/locate (variable point)", "ring: two 16-entry tables (construction + rescale)", "-",
+    names = ["step prologue (scalars, f_j)", "ring step: split + digits", "-", "-", "to-affine (inversion)", "hash + bookkeeping", "ring step: lean doublings (21 x 3, joint table; 12 x 5 with -DS2K_RING_JOINT=0)",
+             "ring step: lean additions + operand decode/locate (variable point)", "ring: the 32-sector table (joint; two 16-entry tables with -DS2K_RING_JOINT=0)", "-",
              "ring step: G and H table additions + leaving the isomorphic curve", "ring: 2^64 * C chain (64 doublings)"]
 tot = v[:12].sum()
 steps = n * 32 * 4 / 64
