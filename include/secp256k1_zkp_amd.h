@@ -236,6 +236,51 @@ S2K_API int secp256k1_ecdsa_adaptor_verify_batch(s2k_engine* e, int32_t* results
 S2K_API int secp256k1_ecdsa_adaptor_verify_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* adaptor_sigs162,
                                                      const unsigned char* pubkeys, const unsigned char* msgs32, const unsigned char* enckeys, int pk_format, size_t n);
 
+/* ---- MuSig2: batch partial-signature verification and nonce processing (the coordinator's half) ------------------------
+ * results[i] = inputs parse &&
+ *              secp256k1_musig_partial_sig_verify(ctx, sig_i, pubnonce_i, pubkey_i, cache_S, session_S),   S = session_of[i]
+ *                                       (include/secp256k1_musig.h, src/modules/musig/session_impl.h:716-777)
+ * partial_sigs   sig_format 0: n*32 serialised (a value >= the group order is refused, as secp256k1_musig_partial_sig_parse);
+ *                1: n*36 `secp256k1_musig_partial_sig` objects (the scalar is reduced, not refused).
+ * pubnonces      nonce_format 0: n*66 serialised as secp256k1_musig_pubnonce_parse reads them (two compressed points; 33 zero bytes
+ *                are NOT accepted); 1: n*132 `secp256k1_musig_pubnonce` objects.
+ * pubkeys        pk_format as in the ECDSA calls (0: n*33, 1: n*64 `secp256k1_pubkey` objects, 2: n*65).
+ * keyagg_caches197, sessions133: n_sessions `secp256k1_musig_keyagg_cache` and `secp256k1_musig_session` objects, one pair per
+ *                signing session; session_of[i] names the pair of share i, so a session with many signers is uploaded once.
+ *                session_of NULL: n_sessions == n and share i uses pair i.
+ * The host and group forms fail with S2K_STATUS_ILLEGAL_ARGUMENT when some session_of[i] >= n_sessions; in the _dev form, where
+ * session_of is device memory like every other array, that share gets verdict 0.  The session's s part and final nonce are not read.
+ * Points inside objects are read as they are: an off-curve point is the caller's error and stays with its item.
+ * DIFFERENCE FROM THE REFERENCE: where secp256k1_musig_partial_sig_verify calls the illegal-argument callback (a wrong magic in any
+ * of the four objects, an all-zero key object) the item gets verdict 0 and its neighbours are unaffected.
+ *
+ * results[i] = inputs parse &&
+ *              secp256k1_musig_nonce_process(ctx, sessions_out133 + 133 i, aggnonce_i, msgs32 + 32 i, cache_i, adaptor_i or NULL)
+ *                                       (session_impl.h:588-638)
+ * aggnonces      nonce_format 0: n*66 serialised as secp256k1_musig_aggnonce_parse reads them (33 zero bytes: infinity);
+ *                1: n*132 `secp256k1_musig_aggnonce` objects.
+ * keyagg_caches197 n*197; adaptors64 NULL (no item has an adaptor) or n*64 `secp256k1_pubkey` objects.
+ * sessions_out133 matches `secp256k1_musig_session` byte for byte and feeds the verifier above, in the _dev forms without leaving
+ * device memory.  DIFFERENCE FROM THE REFERENCE: where results[i] == 0 the session is 133 zero bytes; the reference leaves the
+ * object untouched there (and calls the illegal-argument callback on a wrong magic or an all-zero adaptor object).
+ *
+ * Out of scope, with the reference: everything that touches a secret (nonce_gen*, partial_sign, adapt, extract_adaptor);
+ * pubkey_agg and the cache tweaks (once per key set); nonce_agg and partial_sig_agg (a few additions each). */
+S2K_API int secp256k1_musig_partial_sig_verify_batch(s2k_engine* e, int32_t* results, const unsigned char* partial_sigs, int sig_format,
+                                                     const unsigned char* pubnonces, int nonce_format, const unsigned char* pubkeys, int pk_format,
+                                                     const unsigned char* keyagg_caches197, const unsigned char* sessions133, size_t n_sessions,
+                                                     const uint32_t* session_of, size_t n);
+S2K_API int secp256k1_musig_partial_sig_verify_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* partial_sigs, int sig_format,
+                                                         const unsigned char* pubnonces, int nonce_format, const unsigned char* pubkeys, int pk_format,
+                                                         const unsigned char* keyagg_caches197, const unsigned char* sessions133, size_t n_sessions,
+                                                         const uint32_t* session_of, size_t n);
+S2K_API int secp256k1_musig_nonce_process_batch(s2k_engine* e, int32_t* results, unsigned char* sessions_out133, const unsigned char* aggnonces,
+                                                int nonce_format, const unsigned char* msgs32, const unsigned char* keyagg_caches197,
+                                                const unsigned char* adaptors64, size_t n);
+S2K_API int secp256k1_musig_nonce_process_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* sessions_out133, const unsigned char* aggnonces,
+                                                    int nonce_format, const unsigned char* msgs32, const unsigned char* keyagg_caches197,
+                                                    const unsigned char* adaptors64, size_t n);
+
 /* ---- Whitelist-signature batch verification -------------------------------------------------------------------------
  * results[i] = secp256k1_whitelist_signature_parse(ctx, &sig, sigs + sig_off[i], sig_off[i+1] - sig_off[i]) &&
  *              secp256k1_whitelist_verify(ctx, &sig, online keys of list L, offline keys of list L, length of list L, sub64 + 64 i),   L = list_of[i]
@@ -425,6 +470,11 @@ S2K_API int secp256k1_ecdsa_recover_amd(const void* ctx, void* pubkey, const voi
  * pubkey, enckey: 64-byte secp256k1_pubkey objects. */
 S2K_API int secp256k1_ecdsa_adaptor_verify_amd(const void* ctx, const unsigned char* adaptor_sig162, const void* pubkey, const unsigned char* msg32,
                                                const void* enckey);
+/*   secp256k1_musig_partial_sig_verify(ctx, partial_sig, pubnonce, pubkey, keyagg_cache, session)      include/secp256k1_musig.h,
+ *                                                                                      src/modules/musig/session_impl.h:716
+ * all five point at the reference's objects (36, 132, 64, 197 and 133 bytes). */
+S2K_API int secp256k1_musig_partial_sig_verify_amd(const void* ctx, const void* partial_sig, const void* pubnonce, const void* pubkey, const void* keyagg_cache,
+                                                   const void* session);
 /*   secp256k1_whitelist_verify(ctx, sig, online_pubkeys, offline_pubkeys, n_keys, sub_pubkey)      include/secp256k1_whitelist.h
  * sig: the secp256k1_whitelist_signature object {size_t n_keys; unsigned char data[32 * 256]}; the key arrays: n_keys 64-byte
  * secp256k1_pubkey objects each (they may be NULL when n_keys is 0 here; the reference's ARG_CHECK refuses that). */
@@ -561,6 +611,11 @@ S2K_API int secp256k1_ecdsa_verify_batch_group(s2k_group* g, int32_t* results, c
                                                const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format, size_t n);
 S2K_API int secp256k1_ecdsa_adaptor_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* adaptor_sigs162, const unsigned char* pubkeys,
                                                        const unsigned char* msgs32, const unsigned char* enckeys, int pk_format, size_t n);
+/* (every engine gets its share of the items and the whole cache / session arrays) */
+S2K_API int secp256k1_musig_partial_sig_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* partial_sigs, int sig_format,
+                                                           const unsigned char* pubnonces, int nonce_format, const unsigned char* pubkeys, int pk_format,
+                                                           const unsigned char* keyagg_caches197, const unsigned char* sessions133, size_t n_sessions,
+                                                           const uint32_t* session_of, size_t n);
 S2K_API int secp256k1_xonly_pubkey_tweak_add_check_batch_group(s2k_group* g, int32_t* results, const unsigned char* tweaked32, const unsigned char* parities,
                                                                const unsigned char* internal_keys, int key_format, const unsigned char* tweaks32, size_t n);
 S2K_API int s2k_ecmult_multi_group(s2k_group* g, unsigned char* r_xy, int32_t* r_inf, const unsigned char* g_sc, const unsigned char* sc,

@@ -50,6 +50,10 @@ SIGNATURES = {
     "secp256k1_ecdsa_recover_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "secp256k1_ecdsa_adaptor_verify_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_adaptor_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_musig_partial_sig_verify_batch": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _c.c_int, _vp, _c.c_int, _vp, _vp, _sz, _vp, _sz]),
+    "secp256k1_musig_partial_sig_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _c.c_int, _vp, _c.c_int, _vp, _vp, _sz, _vp, _sz]),
+    "secp256k1_musig_nonce_process_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _vp, _sz]),
+    "secp256k1_musig_nonce_process_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _vp, _sz]),
     "secp256k1_xonly_pubkey_tweak_add_check_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "secp256k1_xonly_pubkey_tweak_add_check_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "secp256k1_pubkey_tweak_add_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
@@ -78,6 +82,7 @@ SIGNATURES = {
     "secp256k1_ecdsa_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "secp256k1_ecdsa_recover_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "secp256k1_ecdsa_adaptor_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "secp256k1_musig_partial_sig_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "secp256k1_whitelist_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _vp]),
     "secp256k1_xonly_pubkey_tweak_add_check_amd": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _vp]),
     "secp256k1_xonly_pubkey_tweak_add_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
@@ -107,6 +112,7 @@ SIGNATURES = {
     "secp256k1_schnorrsig_verify_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_verify_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_adaptor_verify_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_musig_partial_sig_verify_batch_group": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _c.c_int, _vp, _c.c_int, _vp, _vp, _sz, _vp, _sz]),
     "secp256k1_xonly_pubkey_tweak_add_check_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "s2k_ecmult_multi_group": (_c.c_int, [_vp] + [_vp] * 6 + [_sz]),
     "s2k_ecmult_multi_group_dev": (_c.c_int, [_vp] + [_vp] * 7),

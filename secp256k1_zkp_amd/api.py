@@ -83,6 +83,28 @@ def _adaptor_args(what, adaptor_sigs, pubkeys, msgs32, enckeys, pk_format):
     return adaptor_sigs, pubkeys, msgs32, enckeys, n
 
 
+def _musig_verify_args(what, partial_sigs, pubnonces, pubkeys, keyagg_caches, sessions, session_of, sig_format, nonce_format, pk_format):
+    """shape checks shared by Engine.musig_partial_sig_verify and Group.musig_partial_sig_verify; returns the arrays, n_sessions and n"""
+    if sig_format not in (0, 1) or nonce_format not in (0, 1) or pk_format not in _ECDSA_PK_BYTES:
+        raise ValueError(f"{what}: sig_format and nonce_format must be 0 or 1 and pk_format 0, 1 or 2")
+    if partial_sigs is None or pubnonces is None or pubkeys is None or keyagg_caches is None or sessions is None:
+        raise ValueError(f"{what}: missing array")
+    partial_sigs = _u8(partial_sigs); pubnonces = _u8(pubnonces); pubkeys = _u8(pubkeys); keyagg_caches = _u8(keyagg_caches); sessions = _u8(sessions)
+    sgb = 36 if sig_format else 32
+    n = partial_sigs.size // sgb; ns = sessions.size // 133
+    _need(what + " partial_sigs", partial_sigs, sgb * n); _need(what + " pubnonces", pubnonces, (132 if nonce_format else 66) * n)
+    _need(what + " pubkeys", pubkeys, _ECDSA_PK_BYTES[pk_format] * n)
+    _need(what + " sessions", sessions, 133 * ns); _need(what + " keyagg_caches", keyagg_caches, 197 * ns)
+    if session_of is None:
+        if ns != n:
+            raise ValueError(f"{what}: without session_of there is one cache and one session per item ({n}), got {ns}")
+    else:
+        session_of = np.ascontiguousarray(session_of, dtype=np.uint32)
+        if session_of.size != n:
+            raise ValueError(f"{what}: session_of has {session_of.size} entries for {n} items")
+    return partial_sigs, pubnonces, pubkeys, keyagg_caches, sessions, session_of, ns, n
+
+
 _TWEAK_KEY_BYTES = {0: 32, 1: 64, 2: 33}     # serialised x-only / secp256k1_xonly_pubkey or secp256k1_pubkey object / compressed
 
 
@@ -307,6 +329,49 @@ class Engine:
         n = adaptor_sigs.numel() // 162 if n is None else n
         self._check(self._lib.secp256k1_ecdsa_adaptor_verify_batch_dev(self._h, stream, _dp(results), _dp(adaptor_sigs), _dp(pubkeys), _dp(msgs32), _dp(enckeys),
                                                                        pk_format, n), "secp256k1_ecdsa_adaptor_verify_batch_dev")
+
+    # ---- secp256k1_musig_partial_sig_verify and secp256k1_musig_nonce_process (modules/musig/session_impl.h:716-777, :588-638), batched ----
+    def musig_partial_sig_verify(self, partial_sigs, pubnonces, pubkeys, keyagg_caches, sessions, session_of=None, sig_format=0, nonce_format=0, pk_format=0):
+        """partial_sigs n*32 serialised or n*36 objects; pubnonces n*66 serialised or n*132 objects; pubkeys in pk_format (0: n*33, 1: n*64
+        objects, 2: n*65); keyagg_caches n_sessions*197 and sessions n_sessions*133, one pair per signing session; session_of: the pair of
+        each share (uint32), or None when there is one pair per share.  An index >= n_sessions is an error."""
+        partial_sigs, pubnonces, pubkeys, keyagg_caches, sessions, session_of, ns, n = _musig_verify_args(
+            "musig_partial_sig_verify", partial_sigs, pubnonces, pubkeys, keyagg_caches, sessions, session_of, sig_format, nonce_format, pk_format)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_musig_partial_sig_verify_batch(self._h, _p(res), _p(partial_sigs), sig_format, _p(pubnonces), nonce_format, _p(pubkeys), pk_format,
+                                                                       _p(keyagg_caches), _p(sessions), ns, _p(session_of), n), "secp256k1_musig_partial_sig_verify_batch")
+        return res
+
+    def musig_partial_sig_verify_dev(self, results, partial_sigs, pubnonces, pubkeys, keyagg_caches, sessions, n_sessions, session_of=None, sig_format=0, nonce_format=0,
+                                     pk_format=0, n=None, stream=None):
+        """every array in HBM (torch tensors), session_of (int32 / uint32 storage) included; a share whose index is >= n_sessions gets 0"""
+        n = partial_sigs.numel() // (36 if sig_format else 32) if n is None else n
+        self._check(self._lib.secp256k1_musig_partial_sig_verify_batch_dev(self._h, stream, _dp(results), _dp(partial_sigs), sig_format, _dp(pubnonces), nonce_format,
+                                                                           _dp(pubkeys), pk_format, _dp(keyagg_caches), _dp(sessions), n_sessions, _dp(session_of), n),
+                    "secp256k1_musig_partial_sig_verify_batch_dev")
+
+    def musig_nonce_process(self, aggnonces, msgs32, keyagg_caches, adaptors=None, nonce_format=0):
+        """aggnonces n*66 serialised or n*132 objects; msgs32 n*32; keyagg_caches n*197; adaptors None or n*64 secp256k1_pubkey objects.
+        Returns (verdicts, n*133 session bytes); a session whose verdict is 0 is all zero."""
+        if nonce_format not in (0, 1):
+            raise ValueError("musig_nonce_process: nonce_format must be 0 or 1")
+        if aggnonces is None or msgs32 is None or keyagg_caches is None:
+            raise ValueError("musig_nonce_process: missing array")
+        aggnonces = _u8(aggnonces); msgs32 = _u8(msgs32); keyagg_caches = _u8(keyagg_caches); n = msgs32.size // 32
+        _need("musig_nonce_process aggnonces", aggnonces, (132 if nonce_format else 66) * n); _need("musig_nonce_process msgs32", msgs32, 32 * n)
+        _need("musig_nonce_process keyagg_caches", keyagg_caches, 197 * n)
+        if adaptors is not None:
+            adaptors = _u8(adaptors); _need("musig_nonce_process adaptors", adaptors, 64 * n)
+        res = np.zeros(n, np.int32); out = np.zeros(133 * n, np.uint8)
+        self._check(self._lib.secp256k1_musig_nonce_process_batch(self._h, _p(res), _p(out), _p(aggnonces), nonce_format, _p(msgs32), _p(keyagg_caches), _p(adaptors), n),
+                    "secp256k1_musig_nonce_process_batch")
+        return res, out
+
+    def musig_nonce_process_dev(self, results, sessions_out, aggnonces, msgs32, keyagg_caches, adaptors=None, nonce_format=0, n=None, stream=None):
+        """every array in HBM (torch tensors); sessions_out n*133 feeds musig_partial_sig_verify_dev on the same stream"""
+        n = msgs32.numel() // 32 if n is None else n
+        self._check(self._lib.secp256k1_musig_nonce_process_batch_dev(self._h, stream, _dp(results), _dp(sessions_out), _dp(aggnonces), nonce_format, _dp(msgs32),
+                                                                      _dp(keyagg_caches), _dp(adaptors), n), "secp256k1_musig_nonce_process_batch_dev")
 
     # ---- secp256k1_xonly_pubkey_tweak_add_check / _tweak_add (modules/extrakeys/main_impl.h:118-154) and secp256k1_ec_pubkey_tweak_add (secp256k1.c:766-790), batched ----
     def xonly_tweak_add_check_batch(self, tweaked32, parities, internal_keys, tweaks32, key_format=0):
@@ -699,6 +764,15 @@ class Group:
         res = np.zeros(n, np.int32)
         self._check(self._lib.secp256k1_ecdsa_verify_batch_group(self._h, _p(res), _p(sigs), _p(off), sig_format, _p(msghashes), _p(pubkeys), pk_format, n),
                     "secp256k1_ecdsa_verify_batch_group")
+        return res
+
+    def musig_partial_sig_verify(self, partial_sigs, pubnonces, pubkeys, keyagg_caches, sessions, session_of=None, sig_format=0, nonce_format=0, pk_format=0):
+        partial_sigs, pubnonces, pubkeys, keyagg_caches, sessions, session_of, ns, n = _musig_verify_args(
+            "musig_partial_sig_verify_group", partial_sigs, pubnonces, pubkeys, keyagg_caches, sessions, session_of, sig_format, nonce_format, pk_format)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_musig_partial_sig_verify_batch_group(self._h, _p(res), _p(partial_sigs), sig_format, _p(pubnonces), nonce_format, _p(pubkeys),
+                                                                             pk_format, _p(keyagg_caches), _p(sessions), ns, _p(session_of), n),
+                    "secp256k1_musig_partial_sig_verify_batch_group")
         return res
 
     def ecdsa_adaptor_verify_batch(self, adaptor_sigs, pubkeys, msgs32, enckeys, pk_format=0):

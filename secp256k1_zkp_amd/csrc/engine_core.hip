@@ -802,6 +802,20 @@ extern "C" int secp256k1_ecdsa_adaptor_verify_amd(const void* ctx, const unsigne
     if (!secp256k1_ecdsa_adaptor_verify_batch(e, &res, adaptor_sig162, (const unsigned char*)pubkey, msg32, (const unsigned char*)enckey, 1, 1)) return 0;
     return res;
 }
+// include/secp256k1_musig.h (src/modules/musig/session_impl.h:716) -- all five point at the reference's objects (the kernel lives in
+// engine_musig.hip)
+extern "C" int secp256k1_musig_partial_sig_verify_amd(const void* ctx, const void* partial_sig, const void* pubnonce, const void* pubkey, const void* keyagg_cache,
+                                                      const void* session) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!partial_sig || !pubnonce || !pubkey || !keyagg_cache || !session) return s2k_fail_arg("secp256k1_musig_partial_sig_verify_amd", "illegal argument (ARG_CHECK)");
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0;
+    if (!secp256k1_musig_partial_sig_verify_batch(e, &res, (const unsigned char*)partial_sig, 1, (const unsigned char*)pubnonce, 1, (const unsigned char*)pubkey, 1,
+                                                  (const unsigned char*)keyagg_cache, (const unsigned char*)session, 1, nullptr, 1)) return 0;
+    return res;
+}
 // include/secp256k1_recovery.h:112 -- signature points at the 65-byte secp256k1_ecdsa_recoverable_signature object: the little-endian
 // limbs of r and s, then the recovery id (src/modules/recovery/main_impl.h:13-36); pubkey receives a secp256k1_pubkey object
 extern "C" int secp256k1_ecdsa_recover_amd(const void* ctx, void* pubkey, const void* signature, const unsigned char* msghash32) {
@@ -1261,6 +1275,37 @@ extern "C" int secp256k1_ecdsa_adaptor_verify_batch_group(s2k_group* g, int32_t*
         jobs[i] = [=]() -> int {
             if (hi == lo) return 1;
             return secp256k1_ecdsa_adaptor_verify_batch(e, results + lo, adaptor_sigs162 + 162 * lo, pubkeys + pkb * lo, msgs32 + 32 * lo, enckeys + pkb * lo, pk_format, hi - lo);
+        };
+    }
+    const int ok = group_run(g, jobs);
+    if (!ok) memset(results, 0, sizeof(int32_t) * n);
+    return ok;
+}
+// (the items are shared out; every engine uploads the whole cache and session arrays, and session_of is checked here, once)
+extern "C" int secp256k1_musig_partial_sig_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* partial_sigs, int sig_format,
+                                                              const unsigned char* pubnonces, int nonce_format, const unsigned char* pubkeys, int pk_format,
+                                                              const unsigned char* keyagg_caches197, const unsigned char* sessions133, size_t n_sessions,
+                                                              const uint32_t* session_of, size_t n) {
+    const char* who = "secp256k1_musig_partial_sig_verify_batch_group";
+    if (!g || g->eng.empty()) return s2k_fail(who, "null group");
+    if (n == 0) return 1;
+    if (!results || !partial_sigs || !pubnonces || !pubkeys || !keyagg_caches197 || !sessions133) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    if (sig_format < 0 || sig_format > 1 || nonce_format < 0 || nonce_format > 1 || pk_format < 0 || pk_format > 2) return s2k_fail_arg(who, "unknown sig_format / nonce_format / pk_format");
+    if (n_sessions == 0 || (!session_of && n_sessions != n)) return s2k_fail_arg(who, "n_sessions must be n when session_of is NULL, and never 0");
+    if (session_of) for (size_t i = 0; i < n; i++) if (session_of[i] >= n_sessions) return s2k_fail_arg(who, "session_of holds an index >= n_sessions");
+    std::lock_guard<std::mutex> call(g->call_mu);
+    memset(results, 0, sizeof(int32_t) * n);
+    const size_t k = g->eng.size(), sgb = sig_format ? 36 : 32, nb = nonce_format ? 132 : 66, pkb = pk_format == 0 ? 33 : pk_format == 1 ? 64 : 65;
+    std::vector<std::function<int()>> jobs(k);
+    for (size_t i = 0; i < k; i++) {
+        size_t lo, hi; group_share(n, k, i, lo, hi);
+        s2k_engine* e = g->eng[i];
+        jobs[i] = [=]() -> int {
+            if (hi == lo) return 1;
+            if (!session_of) return secp256k1_musig_partial_sig_verify_batch(e, results + lo, partial_sigs + sgb * lo, sig_format, pubnonces + nb * lo, nonce_format, pubkeys + pkb * lo,
+                                                                             pk_format, keyagg_caches197 + 197 * lo, sessions133 + 133 * lo, hi - lo, nullptr, hi - lo);
+            return secp256k1_musig_partial_sig_verify_batch(e, results + lo, partial_sigs + sgb * lo, sig_format, pubnonces + nb * lo, nonce_format, pubkeys + pkb * lo, pk_format,
+                                                            keyagg_caches197, sessions133, n_sessions, session_of + lo, hi - lo);
         };
     }
     const int ok = group_run(g, jobs);

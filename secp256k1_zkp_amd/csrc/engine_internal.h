@@ -15,6 +15,7 @@
 //   engine_tweak.hip       Taproot tweak checks and public-key tweak-add (tweak.h)
 //   engine_generator.hip   asset generators (generate, parse, serialize) and Pedersen commitments to public amounts (generator.h)
 //   engine_adaptor.hip     ECDSA adaptor-signature verification (adaptor.h) and the two-point multiplication s2k_ecmult2_batch
+//   engine_musig.hip       MuSig2 partial-signature verification and nonce processing (musig.h)
 // The per-lane arithmetic lives in the headers next to these files.  No device function is called across translation units (no -fgpu-rdc):
 // a family that needs another family's kernels calls the HOST function that launches them.
 // There is no CPU implementation behind the entry points: without a HIP device every call fails loudly.
