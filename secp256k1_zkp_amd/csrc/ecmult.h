@@ -658,6 +658,8 @@ S2K_HD int ecmult_lane_split(gej& R, const gej& A, const gej& T, const scalar& n
 //     table can be twice as large as ecmult_lane_split's two: 32 sectors of 64 bytes;
 //   * no "key <- key + B", "T <- T + 2^64*B" updates between the steps;
 //   * + W (the table's number of windows) additions from H's table on the steps with j > 0.
+// What the rangeproof rings run is the three-base form further down (ecmult_ring3_tables / ecmult_ring3_step, S2K_RING_TRIPLE in rangeproof.h);
+// it shares the step body, the sizes and the digit-word layout with the joint form described here, which stays for A/B runs.
 // The joint form (S2K_RING_JOINT = 1, the default): ONE table indexed by the digits of BOTH bases.  Its 32 sectors hold
 //     J(a, b) = a*C + b*T ,  a in {1, 3, 5, 7},  b in {+-1, +-3, +-5, +-7} ,  at sector ((a - 1) / 2) * 8 + (b + 7) / 2 ,
 // all on one Z, and a plain operand carries the digit of the C piece and the digit of the T piece of a GLV half at once (the lambda
@@ -722,7 +724,6 @@ S2K_HD int ecmult_lane_split(gej& R, const gej& A, const gej& T, const scalar& n
 #define S2K_RAW_ES (27 * S2K_RAW_WS)
 #define S2K_RRAW_WAVE_WORDS (2 * S2K_RING_ENTRIES * 27 * 64)
 
-#if S2K_RING_JOINT
 // word w .. w + 8 of this lane's column of the parking area
 S2K_HD void rraw_store(u32* raw, int w, const fe& a) {
 #pragma unroll
@@ -735,6 +736,7 @@ S2K_HD void rraw_load(fe& a, const u32* raw, int w) {
 #pragma unroll
     for (int i = 0; i < 9; i++) a.n[i] = (S2K_NT_PARK && S2K_RAW_WS > 1) ? S2K_LD_NT(&raw[(w + i) * S2K_RAW_WS]) : raw[(w + i) * S2K_RAW_WS];
 }
+#if S2K_RING_JOINT
 #define S2K_RJ_CHAIN_SLOT 24                                    /* the two raw chains: slots 24..27 (C) and 28..31 (T) of the parking area */
 #define S2K_RJ_PAIR0 144                                        /* first word of pair 0 */
 #define S2K_RJ_PAIR_WORDS 45
@@ -857,36 +859,242 @@ S2K_HD void ecmult_ring_tables(u32* rtab, u32* raw, const gej& C, const gej& T) 
     for (int i = 0; i < 9; i++) rtab[S2K_RTAB_ZISO + i] = ziso.n[i];
 }
 #endif
+// ---- the three-base form of the ring table (S2K_RING_TRIPLE, rangeproof.h) -------------------------------------------------------
+// Every odd GLV half k < 2^129 is cut into THREE 43-bit pieces, k = p0 + 2^43 p1 + 2^86 p2, over the bases C, T1 = 2^43*C and T2 = 2^86*C.
+// From the top down each piece is made odd by the borrow of sc_split_pieces (+1 on it, -2^43 on the piece below it), so a piece carries
+// its own sign and every magnitude is odd and below 2^43.  A piece becomes 22 signed odd 2-bit digits d_i = 2 b_i - 3:
+// sum d_i 4^i = 2B - (2^44 - 1), so b is read off B = (v - 1)/2 + 2^43 -- bit t of B is bit t + 1 of v and bit 43 is set -- which represents
+// every odd v <= 2^44 - 1 with no fixed top digit.  Level i of a half has the signed digits (dC, d1, d2) in {+-1, +-3}^3 and takes
+//     sign(dC) * J(|dC|, sign(dC) d1, sign(dC) d2) ,   J(a, b, c) = a*C + b*T1 + c*T2 ,  a in {1, 3},  b, c in {+-1, +-3} ,
+// at sector ((a - 1) / 2) * 16 + ((b + 3) / 2) * 4 + (c + 3) / 2: the same 32 sectors, and the same six-bit field neg << 5 | sector at
+// the same place (level * 2 + half, five per word) that ecmult_ring_step's operand lookup reads for the joint form.
+// A step is 22 levels of 2 doublings (none in front of the first) + 2 additions: 42 doublings, 44 additions, 22 beta products; the
+// chain is 86 doublings per ring instead of 64.
+// Construction (ecmult_ring3_tables): three 2-entry chains {P, 3P} of C, T1 and T2 (ptab_build_raw_n<2>) rescaled to one Z (za z1 z2);
+// stage 1: the four conjugate pairs b*T1 +- c*T2 (b, c in {1, 3}), brought to the product D1 of their four dx, which gives the eight
+// Q = b*T1 + c*T2 with b > 0 (q = 4 (b - 1)/2 + 2 (|c| - 1)/2 + (c < 0)), and C, 3C rescaled by D1; stage 2: the sixteen conjugate
+// pairs a*C +- Q (pair k = 8 (a - 1)/2 + q: a*C + Q = J(a, b, c), a*C - Q = J(a, -b, -c)), brought to the product D2 of their sixteen dx
+// by prefix / suffix products and packed.  The Z factor is za z1 z2 D1 D2.  No addition in it can be exceptional for a finite C (a
+// coincidence needs n to divide a small nonzero odd combination of 1, 2^43 and 2^86); a dx of zero ends up as a factor of the Z factor
+// all the same, and a step that finds the Z factor zero returns 0.
+// A lane's 32 x 27 words of the parking area (word w at raw[w * S2K_RAW_WS]) during the construction:
+//     words   0..35   C, 3C, 18 words (x, y) each: on the chains' Z, then on D1
+//     words  36..179  Q_0..Q_7, 18 words each (written by the backward pass of stage 1)
+//     words 180..854  stage 2: pair k = 0..14, 45 words (x+, y+, x-, y-, product of the dx before it); pair 15 is never parked: the
+//                     forward pass hands it to the backward pass in registers, which is what makes 36 + 144 + 15 * 45 = 855 <= 864
+//     before stage 2 the same words hold: 180..251 T1, 3T1, T2, 3T2 (18 words each, rescaled), 300..479 the four pairs of stage 1,
+//     702..863 the three chains as ptab_build_raw_n parks them (6 slots of 27 words)
+struct piece43 { u64 m; int neg; };
+#define S2K_R3_DIGITS 22
+#define S2K_R3_Q0 36
+#define S2K_R3_PAIR0 180
+#define S2K_R3_T0 180
+#define S2K_R3_S1PAIR0 300
+#define S2K_R3_CHAIN0 702
+#define S2K_R3_PAIR_WORDS 45
+// out[0], out[1] = C pieces of k1, k2; out[2], out[3] = T1 pieces; out[4], out[5] = T2 pieces (sign of the half folded in)
+S2K_HD void sc_split_pieces3(piece43 out[6], const half_scalar& h0, const half_scalar& h1) {
+    const u64 mask = (1ull << 43) - 1ull;
+    for (int hf = 0; hf < 2; hf++) {
+        const half_scalar& h = hf ? h1 : h0;
+        const u64 lo = (u64)h.w[0] | ((u64)h.w[1] << 32), mid = (u64)h.w[2] | ((u64)h.w[3] << 32);
+        long long p0 = (long long)(lo & mask);
+        long long p1 = (long long)(((lo >> 43) | (mid << 21)) & mask);
+        long long p2 = (long long)((mid >> 22) | ((u64)h.w[4] << 42));            // k >> 86 (< 2^43)
+        if (!(p2 & 1)) { p2 += 1; p1 -= (long long)(1ull << 43); }                // top piece odd: +1 on it, -2^43 on the one below
+        if (!(p1 & 1)) { p1 += 1; p0 -= (long long)(1ull << 43); }                // (p0 is odd as k is: p0 - 2^43 is odd and nonzero)
+        const long long p[3] = {p0, p1, p2};
+        for (int b = 0; b < 3; b++) { out[2 * b + hf].m = (u64)(p[b] < 0 ? -p[b] : p[b]); out[2 * b + hf].neg = (p[b] < 0) ^ h.neg; }
+    }
+}
+// the 2-bit field b_i (digit d_i = 2 b_i - 3, i = 0 least significant) of an odd piece magnitude <= 2^44 - 1
+S2K_HD u32 ring3_piece_field(u64 m, int i) { return (u32)((((m >> 1) | (1ull << 43)) >> (2 * i)) & 3ull); }
+// fields vc, v1, v2 of the pieces on C, T1, T2 at one level, sc, s1, s2 their signs (1 = negative)  ->  neg << 5 | sector
+S2K_HD u32 ring3_field(u32 vc, u32 v1, u32 v2, u32 sc, u32 s1, u32 s2) {
+    const u32 neg = (u32)(vc < 2u) ^ sc;
+    const u32 ai = vc < 2u ? 1u - vc : vc - 2u;                 // (|dC| - 1) / 2
+    const u32 bi = v1 ^ ((neg ^ s1) ? 3u : 0u);                 // (b + 3) / 2 ; negating b = 2 v - 3 is v -> 3 - v
+    const u32 ci = v2 ^ ((neg ^ s2) ? 3u : 0u);
+    return (neg << 5) | (ai << 4) | (bi << 2) | ci;
+}
+// the digit words 0..8 of a step: field (level * 2 + half), level 0 = most significant, five six-bit fields per word
+S2K_HD void ring3_recode(u32 dw[9], const piece43 pc[6]) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) dw[i] = 0;
+#pragma unroll
+    for (int hf = 0; hf < 2; hf++) {
+#pragma unroll
+        for (int pos = 0; pos < S2K_R3_DIGITS; pos++) {
+            const int i = S2K_R3_DIGITS - 1 - pos, idx = pos * 2 + hf;
+            const u32 v = ring3_field(ring3_piece_field(pc[hf].m, i), ring3_piece_field(pc[2 + hf].m, i), ring3_piece_field(pc[4 + hf].m, i),
+                                      (u32)pc[hf].neg, (u32)pc[2 + hf].neg, (u32)pc[4 + hf].neg);
+            dw[idx / 5] |= v << ((idx % 5) * 6);
+        }
+    }
+}
+// One batch of N conjugate pairs P1 +- P2 (both affine on one curve: 18 parked words (x, y) each, pair k taking the words from w1(k) and
+// w2(k)): forward, both sums at Z = dx = x2 - x1 (5M + 3S the pair) parked at rec0 + 45 k with the product of the dx before them; backward,
+// every pair times the product of the OTHER dx -- all of them on Z = prod dx -- handed to out(k, x+, y+, x-, y-).  s: prod dx.
+// KEEP_LAST: pair N - 1 is not parked (rec0 .. rec0 + 45 (N - 1) - 1 is all that is written); it stays in registers between the passes.
+struct ring3_pair { fe xp, yp, xm, ym, m, dx; };
+S2K_HD void ring3_pair_add(ring3_pair& r, const u32* raw, int w1o, int w2o) {
+    fe x1, y1, x2, y2;
+    rraw_load(x1, raw, w1o); rraw_load(y1, raw, w1o + 9); rraw_load(x2, raw, w2o); rraw_load(y2, raw, w2o + 9);
+    fe dy, sy, t, c, d, d2, w1, w2, e, a1;
+    fe_neg(t, x1, 1); fe_add2(r.dx, x2, t); fe_norm_weak(r.dx);
+    fe_neg(t, y1, 1); fe_add2(dy, y2, t); fe_norm_weak(dy);
+    fe_add2(sy, y1, y2); fe_norm_weak(sy);
+    fe_sqr2(c, r.dx, d, dy);
+    fe_mul2(w1, x1, c, w2, x2, c);
+    fe_neg(e, w1, 1); fe_add(e, w2);                                  // dx^3                        (3)
+    fe_mul_sqr(a1, y1, e, d2, sy);                                    // (1*3)
+    fe_add2(t, w1, w2); fe_neg(t, t, 2);                              // -(W1 + W2)                  (3)
+    fe_add2(r.xp, d, t); fe_add2(r.xm, d2, t);                        // X(P1 + P2), X(P1 - P2)      (4)
+    fe_neg(t, r.xp, 4); fe_add(t, w1);                                // W1 - X3                     (6)
+    fe_neg(e, w1, 1); fe_add(e, r.xm);                                // X3' - W1                    (6)
+    fe_mul2(r.yp, dy, t, r.ym, sy, e);                                // (1*6, 1*6)
+    fe_neg(t, a1, 1); fe_add(r.yp, t); fe_add(r.ym, t);               // Y = dy (W1 - X3) - y1 dx^3 ; Y' = sy (X3' - W1) - y1 dx^3   (3)
+}
+// pair r (m = product of the dx before it) times s (product of the dx behind it); s takes the pair's own dx in
+S2K_HD void ring3_pair_scale(ring3_pair& r, fe& s) {
+    fe m;
+    fe_mul2(m, r.m, s, s, s, r.dx);
+    fe m2, m3; fe_sqr(m2, m); fe_mul(m3, m2, m);
+    fe_mul2(r.xp, r.xp, m2, r.xm, r.xm, m2);                          // (4*1)
+    fe_mul2(r.yp, r.yp, m3, r.ym, r.ym, m3);                          // (3*1)
+}
+template <int N, int KEEP_LAST, class W1, class W2, class Out>
+S2K_HD void ring3_pair_batch(fe& s, u32* raw, int rec0, W1 w1, W2 w2, Out out) {
+    ring3_pair r;
+    fe p; fe_set_int(p, 1);
+#pragma unroll 1
+    for (int k = 0; k < N - KEEP_LAST; k++) {
+        const int rec = rec0 + S2K_R3_PAIR_WORDS * k;
+        ring3_pair_add(r, raw, w1(k), w2(k));
+        rraw_store(raw, rec, r.xp); rraw_store(raw, rec + 9, r.yp); rraw_store(raw, rec + 18, r.xm); rraw_store(raw, rec + 27, r.ym);
+        rraw_store(raw, rec + 36, p);
+        fe_mul(p, p, r.dx);
+    }
+    fe_set_int(s, 1);
+    if (KEEP_LAST) {
+        ring3_pair_add(r, raw, w1(N - 1), w2(N - 1));
+        r.m = p;
+        ring3_pair_scale(r, s);
+        out(N - 1, r);
+    }
+#pragma unroll 1
+    for (int k = N - 1 - KEEP_LAST; k >= 0; k--) {
+        const int rec = rec0 + S2K_R3_PAIR_WORDS * k;
+        rraw_load(r.xp, raw, rec); rraw_load(r.yp, raw, rec + 9); rraw_load(r.xm, raw, rec + 18); rraw_load(r.ym, raw, rec + 27); rraw_load(r.m, raw, rec + 36);
+        fe x1; rraw_load(x1, raw, w1(k)); rraw_load(r.dx, raw, w2(k));
+        fe_neg(x1, x1, 1); fe_add(r.dx, x1); fe_norm_weak(r.dx);
+        ring3_pair_scale(r, s);
+        out(k, r);
+    }
+}
+// C, T1 = 2^43*C, T2 = 2^86*C finite, magnitudes <= (5,3,1).  rtab: this lane's S2K_RTAB_WORDS; raw: this lane's column of its wavefront's
+// parking area
+S2K_HD void ecmult_ring3_tables(u32* rtab, u32* raw, const gej& C, const gej& T1, const gej& T2) {
+    {   // the chains, all on the Z  za * z1 * z2  (which waits in the Z factor's place)
+        fe za, z1, z2, zoa, zo1, zo2, zs;
+        ptab_build_raw_n<2, S2K_RAW_WS, S2K_RAW_ES>(za, raw + S2K_R3_CHAIN0 * S2K_RAW_WS, C);
+        ptab_build_raw_n<2, S2K_RAW_WS, S2K_RAW_ES>(z1, raw + (S2K_R3_CHAIN0 + 54) * S2K_RAW_WS, T1);
+        ptab_build_raw_n<2, S2K_RAW_WS, S2K_RAW_ES>(z2, raw + (S2K_R3_CHAIN0 + 108) * S2K_RAW_WS, T2);
+        fe_mul2(zoa, z1, z2, zo1, za, z2);                          // each chain by the product of the OTHER two's Z
+        fe_mul(zo2, za, z1);
+#pragma unroll 1
+        for (int e = 5; e >= 0; e--) {
+            if (e == 5) zs = zo2; else if (e == 3) zs = zo1; else if (e == 1) zs = zoa;
+            const int src = S2K_R3_CHAIN0 + 27 * e, dst = e < 2 ? 18 * e : S2K_R3_T0 + 18 * (e - 2);
+            fe x, y, h, zs2, zs3;
+            rraw_load(x, raw, src); rraw_load(y, raw, src + 9); rraw_load(h, raw, src + 18);
+            fe_sqr(zs2, zs); fe_mul(zs3, zs2, zs);
+            fe_mul2(x, x, zs2, y, y, zs3);
+            rraw_store(raw, dst, x); rraw_store(raw, dst + 9, y);
+            fe_mul(zs, zs, h);                                      // ratio z_1 / z_0 joins the factor for the entry below
+        }
+        fe_mul(zs, zoa, za);
+#pragma unroll
+        for (int i = 0; i < 9; i++) rtab[S2K_RTAB_ZISO + i] = zs.n[i];
+    }
+    fe d1, d2;
+    // stage 1: pair k = 2 (b - 1)/2 + (c - 1)/2 : b*T1 +- c*T2  ->  Q_2k = b*T1 + c*T2, Q_2k+1 = b*T1 - c*T2
+    ring3_pair_batch<4, 0>(d1, raw, S2K_R3_S1PAIR0,
+        [](int k) { return S2K_R3_T0 + 18 * (k >> 1); }, [](int k) { return S2K_R3_T0 + 36 + 18 * (k & 1); },
+        [&](int k, const ring3_pair& r) {
+            const int q = S2K_R3_Q0 + 36 * k;
+            rraw_store(raw, q, r.xp); rraw_store(raw, q + 9, r.yp); rraw_store(raw, q + 18, r.xm); rraw_store(raw, q + 27, r.ym);
+        });
+    {   // C, 3C onto D1
+        fe m2, m3; fe_sqr(m2, d1); fe_mul(m3, m2, d1);
+#pragma unroll 1
+        for (int e = 0; e < 2; e++) {
+            fe x, y; rraw_load(x, raw, 18 * e); rraw_load(y, raw, 18 * e + 9);
+            fe_mul2(x, x, m2, y, y, m3);
+            rraw_store(raw, 18 * e, x); rraw_store(raw, 18 * e + 9, y);
+        }
+    }
+    // stage 2: pair k = 8 (a - 1)/2 + q : a*C +- Q_q, normalised and packed, two sectors the pair
+    ring3_pair_batch<16, 1>(d2, raw, S2K_R3_PAIR0,
+        [](int k) { return 18 * (k >> 3); }, [](int k) { return S2K_R3_Q0 + 18 * (k & 7); },
+        [&](int k, ring3_pair& r) {
+            const int ai = k >> 3, bi = 2 + ((k >> 2) & 1), ca = (k >> 1) & 1, ci = (k & 1) ? 1 - ca : 2 + ca;      // (b + 3) / 2, (c + 3) / 2
+            fe_normalize(r.xp); fe_normalize(r.yp); fe_normalize(r.xm); fe_normalize(r.ym);
+            u32* const ep = rtab + (ai * 16 + bi * 4 + ci) * 16;                  // J(a, b, c)
+            u32* const em = rtab + (ai * 16 + (3 - bi) * 4 + (3 - ci)) * 16;      // J(a, -b, -c)
+            u32 wx[8], wy[8];
+            fe_to_words(wx, r.xp); fe_to_words(wy, r.yp);
+#pragma unroll
+            for (int i = 0; i < 8; i++) { ep[i] = wx[i]; ep[8 + i] = wy[i]; }
+            fe_to_words(wx, r.xm); fe_to_words(wy, r.ym);
+#pragma unroll
+            for (int i = 0; i < 8; i++) { em[i] = wx[i]; em[8 + i] = wy[i]; }
+        });
+    fe ziso;
+#pragma unroll
+    for (int i = 0; i < 9; i++) ziso.n[i] = rtab[S2K_RTAB_ZISO + i];
+    fe_mul(d1, d1, d2); fe_mul(ziso, ziso, d1);                               // (a dx of zero makes the Z factor zero: the step then returns 0)
+#pragma unroll
+    for (int i = 0; i < 9; i++) rtab[S2K_RTAB_ZISO + i] = ziso.n[i];
+}
 // e != 0; has_f uniform over the wavefront.  htab: this lane's generator's table (same layout as gtab).
-S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scalar& s, const scalar& f, int has_f, const u32* gtab, const u32* htab,
-                            const s2k_lds_ptr dig) {
-#if !S2K_RING_JOINT
-    u32 sneg = 0;
+// the digit words 0..8 of a step of the two-base forms from the GLV halves (joint form: ring_joint_recode; separate form: 5-bit digits
+// (pos * 4 + stream), six per word, and the streams' signs in sneg)
+S2K_HD void ring_step_recode(u32 dw[9], u32& sneg, const half_scalar& h0, const half_scalar& h1) {
+    piece65 pc[4]; sc_split_pieces(pc, h0, h1);
+#if S2K_RING_JOINT
+    ring_joint_recode(dw, pc);
+#else
+#pragma unroll
+    for (int i = 0; i < 9; i++) dw[i] = 0;
+#pragma unroll
+    for (int st = 0; st < 4; st++) {
+        sneg |= (u32)pc[st].neg << st;
+#pragma unroll
+        for (int pos = 0; pos < S2K_RING_DIGITS; pos++) {            // pos 0 = most significant digit
+            const int i = S2K_RING_DIGITS - 1 - pos, bit = S2K_RING_W * i + 1, word = bit >> 5, sh = bit & 31;
+            const u64 pair = (u64)pc[st].w[word] | ((u64)(word + 1 < 3 ? pc[st].w[word + 1] : 0u) << 32);
+            u32 v = (u32)(pair >> sh) & 31u;
+            if (pos == 0) v |= 16u;                                  // bit 64 of B (the piece is below 2^65: bits 65, 66 are clear)
+            const int nib = pos * 4 + st;
+            dw[nib / 6] |= v << ((nib % 6) * 5);
+        }
+    }
 #endif
+}
+// TRIPLE = 1: the three-base form (above): 2 doublings a level and its own recoding; the fields sit where the joint form's do.
+template <int TRIPLE>
+S2K_HD int ecmult_ring_step_t(gej& R, const u32* rtab, const scalar& e, const scalar& s, const scalar& f, int has_f, const u32* gtab, const u32* htab,
+                              const s2k_lds_ptr dig) {
+    constexpr int RING_W = TRIPLE ? 2 : S2K_RING_W, RING_GROUP = TRIPLE ? 2 : S2K_RING_GROUP, RING_ADDS_P = TRIPLE ? 2 * S2K_R3_DIGITS : S2K_RING_ADDS_P;
+    constexpr bool FIELDS = TRIPLE || S2K_RING_JOINT;           // six-bit fields neg << 5 | sector in the digit words
+    u32 sneg = 0; (void)sneg;                                   // (separate form only)
     S2K_PROF_DECL;
     {
         half_scalar h0, h1; sc_split_lambda_odd(h0, h1, e);
-        piece65 pc[4]; sc_split_pieces(pc, h0, h1);
         u32 dw[9];
-#if S2K_RING_JOINT
-        ring_joint_recode(dw, pc);
-#else
-#pragma unroll
-        for (int i = 0; i < 9; i++) dw[i] = 0;
-#pragma unroll
-        for (int st = 0; st < 4; st++) {
-            sneg |= (u32)pc[st].neg << st;
-#pragma unroll
-            for (int pos = 0; pos < S2K_RING_DIGITS; pos++) {            // pos 0 = most significant digit
-                const int i = S2K_RING_DIGITS - 1 - pos, bit = S2K_RING_W * i + 1, word = bit >> 5, sh = bit & 31;
-                const u64 pair = (u64)pc[st].w[word] | ((u64)(word + 1 < 3 ? pc[st].w[word + 1] : 0u) << 32);
-                u32 v = (u32)(pair >> sh) & 31u;
-                if (pos == 0) v |= 16u;                                  // bit 64 of B (the piece is below 2^65: bits 65, 66 are clear)
-                const int nib = pos * 4 + st;
-                dw[nib / 6] |= v << ((nib % 6) * 5);
-            }
-        }
-#endif
+        if constexpr (TRIPLE) { piece43 pc3[6]; sc_split_pieces3(pc3, h0, h1); ring3_recode(dw, pc3); }
+        else ring_step_recode(dw, sneg, h0, h1);
 #pragma unroll
         for (int i = 0; i < 9; i++) dig[i * S2K_DIG_STRIDE] = dw[i];
         u32 sr[S2K_GTAB_SWORDS], fr[S2K_GTAB_SWORDS]; gtab_recode(sr, s.d, gtab); gtab_recode(fr, f.d, has_f ? htab : gtab);
@@ -895,24 +1103,24 @@ S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scal
     }
     S2K_PROF_MARK(1);
     const gtab_geom GG = gtab_geometry(gtab), GH = gtab_geometry(has_f ? htab : gtab);      // (the generator's table may have another width than G's)
-    const int a_g0 = S2K_RING_ADDS_P, a_h0 = a_g0 + (int)GG.W;
+    const int a_g0 = RING_ADDS_P, a_h0 = a_g0 + (int)GG.W;
     const int a_end = has_f ? a_h0 + (int)GH.W : a_h0;
     auto op_locate = [&](const u32*& addr, int& valid, int& neg, int idx) {
         addr = rtab; valid = 0; neg = 0;
         if (idx < a_g0) {
-#if S2K_RING_JOINT
-            const u32 v = (dig[(idx / 5) * S2K_DIG_STRIDE] >> ((idx % 5) * 6)) & 63u;       // ring_joint_field
-            valid = 1;
-            neg = (int)(v >> 5);
-            addr = rtab + (v & 31u) * 16;
-#else
-            const int st = idx & 3;
-            const u32 v = (dig[(idx / 6) * S2K_DIG_STRIDE] >> ((idx % 6) * 5)) & 31u;
-            valid = 1;
-            neg = (v < 16u) ^ (int)((sneg >> st) & 1u);
-            const u32 en = (v < 16u) ? (15u - v) : (v - 16u);
-            addr = rtab + (st >> 1) * S2K_RTAB_TABLE_WORDS + en * 16;
-#endif
+            if constexpr (FIELDS) {
+                const u32 v = (dig[(idx / 5) * S2K_DIG_STRIDE] >> ((idx % 5) * 6)) & 63u;   // ring_joint_field / ring3_field
+                valid = 1;
+                neg = (int)(v >> 5);
+                addr = rtab + (v & 31u) * 16;
+            } else {
+                const int st = idx & 3;
+                const u32 v = (dig[(idx / 6) * S2K_DIG_STRIDE] >> ((idx % 6) * 5)) & 31u;
+                valid = 1;
+                neg = (v < 16u) ^ (int)((sneg >> st) & 1u);
+                const u32 en = (v < 16u) ? (15u - v) : (v - 16u);
+                addr = rtab + (st >> 1) * S2K_RTAB_TABLE_WORDS + en * 16;
+            }
         } else if (idx < a_end) {
             const int second = idx >= a_h0;
             const int g = idx - (second ? a_h0 : a_g0), base = second ? 18 : 9, w = (int)(((u32)g * (second ? GH.D : GG.D)) >> 5);
@@ -935,13 +1143,14 @@ S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scal
     op_decode(cur, raw, nxt_neg, 0);
     op_locate(nxt_addr, nxt_valid, nxt_neg, 1);
     // variable part, separate form: additions 0..51 as 26 (plain stream, lambda stream) pairs, 5 doublings in front of every group of four
-    // but the first; joint form: additions 0..43 as 22 such pairs, one per level, 3 doublings in front of every pair but the first
+    // but the first; joint form: additions 0..43 as 22 such pairs, one per level, 3 doublings in front of every pair but the first (three-base
+    // form: 2 doublings)
     int au = 0;
     while (au < a_g0) {
-        if (au >= S2K_RING_GROUP && !(au & (S2K_RING_GROUP - 1))) {
+        if (au >= RING_GROUP && !(au & (RING_GROUP - 1))) {
             S2K_PROF_MARK(7);
 #pragma unroll 1
-            for (int k = 0; k < S2K_RING_W; k++) gej_double_lean(R, R);
+            for (int k = 0; k < RING_W; k++) gej_double_lean(R, R);
             S2K_PROF_MARK(6);
         }
 #pragma unroll
@@ -965,8 +1174,8 @@ S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scal
         fe_mul(R.z, R.z, zi);
         // a Z factor of zero (joint form: a table whose construction met a dx of zero) makes ZZ zero below, it stays zero through the table
         // part, and the one ZZ test behind it sends the step back; only the form without that test needs one of its own
-#if S2K_RING_JOINT && !S2K_XYZZ_TABLE_PART
-        if (S2K_WAVE_ANY(fe_normalizes_to_zero(zi))) return 0;
+#if !S2K_XYZZ_TABLE_PART
+        if (FIELDS && S2K_WAVE_ANY(fe_normalizes_to_zero(zi))) return 0;
 #endif
     }
     // table part (G, then H): a zero window adds nothing (per lane), so these additions are committed by select
@@ -1010,6 +1219,14 @@ S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scal
     S2K_ON_RING_STEP_DONE();
 #endif
     return 1;
+}
+S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scalar& s, const scalar& f, int has_f, const u32* gtab, const u32* htab,
+                            const s2k_lds_ptr dig) {
+    return ecmult_ring_step_t<0>(R, rtab, e, s, f, has_f, gtab, htab, dig);
+}
+S2K_HD int ecmult_ring3_step(gej& R, const u32* rtab, const scalar& e, const scalar& s, const scalar& f, int has_f, const u32* gtab, const u32* htab,
+                             const s2k_lds_ptr dig) {
+    return ecmult_ring_step_t<1>(R, rtab, e, s, f, has_f, gtab, htab, dig);
 }
 
 

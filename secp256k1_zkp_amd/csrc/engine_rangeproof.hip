@@ -801,3 +801,5 @@ extern "C" __attribute__((visibility("default"))) int s2k_prof_read(unsigned lon
     return hipMemcpyToSymbol(HIP_SYMBOL(s2k_prof_slots), z, sizeof(z)) == hipSuccess;
 }
 #endif
+// which ring table k_rp_rings_shared was built with: 1 = three bases (S2K_RING_TRIPLE, rangeproof.h), 0 = the joint table of two
+extern "C" __attribute__((visibility("default"))) int s2k_ring_triple(void) { return S2K_RING_TRIPLE; }

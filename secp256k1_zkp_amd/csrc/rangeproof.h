@@ -528,6 +528,16 @@ S2K_HD int rp_ring_suspect(const gej& C, const u32* xmul /* this (exp, ring)'s 3
 #define S2K_RP_K 1                      /* rings per lane in the engine's shared-generator kernel; K > 1 shares the inversion of a ring position between K
                                            rings but keeps K times the tables alive: measured on MI355X 15.5 (K=1) / 15.75 (2) / 15.85 ms (4) per 2^14 proofs */
 #endif
+// S2K_RING_TRIPLE: the ring table over three bases C, 2^43 C, 2^86 C (ecmult.h: ecmult_ring3_tables, 42 doublings a step, an 86-doubling
+// chain a ring) instead of the joint table over C and 2^64 C (63 and 64); 0 = the joint form, for A/B runs.
+#ifndef S2K_RING_TRIPLE
+#define S2K_RING_TRIPLE 1
+#endif
+#if S2K_RING_TRIPLE
+#define S2K_RP_RING_STEP ecmult_ring3_step
+#else
+#define S2K_RP_RING_STEP ecmult_ring_step
+#endif
 #define RP_SHARED_SUSPECT 0
 #define RP_SHARED_SERVED 1
 #define RP_SHARED_EXCEPTIONAL 2
@@ -581,11 +591,24 @@ S2K_HD int rp_rings_shared(const rp_rec& rec, const u32* pub28, unsigned char* r
         S2K_PROF_RESET;
         gej T = C;
         // dbg (diagnostic launches only, $S2K_RP_DEBUG; results are then meaningless): bit 0 = no chain, bit 1 = no tables, bit 2 = no steps
+#if S2K_RING_TRIPLE
+        gej T1;                                                     // T1 = 2^43 C, T = 2^86 C
+#pragma unroll 1
+        for (int h = 0; h < 2; h++) {
+#pragma unroll 1
+            for (int k = 0; k < ((dbg & 1u) ? 0 : 43); k++) gej_double_lean(T, T);
+            fe_norm_weak(T.y);
+            if (h == 0) T1 = T;
+        }
+        S2K_PROF_MARK(11);
+        if (!(dbg & 2u)) ecmult_ring3_tables(M.rtab + (size_t)q * S2K_RTAB_WORDS, M.raw, C, T1, T);
+#else
 #pragma unroll 1
         for (int k = 0; k < ((dbg & 1u) ? 0 : 64); k++) gej_double_lean(T, T);
         fe_norm_weak(T.y);
         S2K_PROF_MARK(11);
         if (!(dbg & 2u)) ecmult_ring_tables(M.rtab + (size_t)q * S2K_RTAB_WORDS, M.raw, C, T);
+#endif
         S2K_PROF_MARK(8);
     }
     if (dbg & 4u) return RP_SHARED_SERVED;
@@ -622,7 +645,7 @@ S2K_HD int rp_rings_shared(const rp_rec& rec, const u32* pub28, unsigned char* r
             S2K_PROF_MARK(0);
             // an exceptional addition somewhere in the wavefront (an operand with the accumulator's own x: adversarial inputs only): everything
             // goes back to the caller, i.e. to the general form, which starts the rings over on the keys themselves
-            if (!S2K_WAVE_ALL(ecmult_ring_step(R, M.rtab + (size_t)q * S2K_RTAB_WORDS, ens, s, f, j > 0, gtab, htab, M.dig))) return RP_SHARED_EXCEPTIONAL;
+            if (!S2K_WAVE_ALL(S2K_RP_RING_STEP(R, M.rtab + (size_t)q * S2K_RTAB_WORDS, ens, s, f, j > 0, gtab, htab, M.dig))) return RP_SHARED_EXCEPTIONAL;
             S2K_PROF_RESET;
             fe_norm_weak(R.x); fe_norm_weak(R.y);
 #pragma unroll

@@ -31,9 +31,9 @@ names = ["step prologue (key load, next key, T update)", "ecmult: split + digits
          "hash + bookkeeping", "main loop: 4 lean doublings", "main loop: lean addition + operand decode/locate", "split: 2 x co-Z table construction",
          "split: 2 x table rescale", "split: generator additions + leaving the isomorphic curve", "ring: 2^64 * key chain (64 doublings)"]
 if os.environ.get("S2K_GEN_CACHE", "") != "0":        # the shared-generator form of the kernel (rp_ring_shared / ecmult_ring_step) uses the slots like this
-    names = ["step prologue (scalars, f_j)", "ring step: split + digits", "-", "-", "to-affine (inversion)", "hash + bookkeeping", "ring step: lean doublings (21 x 3, joint table; 12 x 5 with -DS2K_RING_JOINT=0)",
-             "ring step: lean additions + operand decode/locate (variable point)", "ring: the 32-sector table (joint; two 16-entry tables with -DS2K_RING_JOINT=0)", "-",
-             "ring step: G and H table additions + leaving the isomorphic curve", "ring: 2^64 * C chain (64 doublings)"]
+    names = ["step prologue (scalars, f_j)", "ring step: split + digits", "-", "-", "to-affine (inversion)", "hash + bookkeeping", "ring step: lean doublings (21 x 2, three-base table; 21 x 3 with -DS2K_RING_TRIPLE=0, the joint table)",
+             "ring step: lean additions + operand decode/locate (variable point)", "ring: the 32-sector table (three bases C, 2^43 C, 2^86 C; the joint table of C and 2^64 C with -DS2K_RING_TRIPLE=0)", "-",
+             "ring step: G and H table additions + leaving the isomorphic curve", "ring: chain to 2^43 * C and 2^86 * C (86 doublings; to 2^64 * C, 64 doublings, with -DS2K_RING_TRIPLE=0)"]
 tot = v[:12].sum()
 steps = n * 32 * 4 / 64
 out = {("%d: " % i) + names[i]: {"wave_cycles": v[i], "share": round(v[i] / tot, 4), "cycles_per_wave_step": round(v[i] / steps)} for i in range(12)}
