@@ -877,21 +877,27 @@ S2K_HD void ecmult_ring_tables(u32* rtab, u32* raw, const gej& C, const gej& T) 
 // by prefix / suffix products and packed.  The Z factor is za z1 z2 D1 D2.  No addition in it can be exceptional for a finite C (a
 // coincidence needs n to divide a small nonzero odd combination of 1, 2^43 and 2^86); a dx of zero ends up as a factor of the Z factor
 // all the same, and a step that finds the Z factor zero returns 0.
-// A lane's 32 x 27 words of the parking area (word w at raw[w * S2K_RAW_WS]) during the construction:
+// The sums of a pair are never parked: Z = dx of a pair is a difference of two parked inputs, so a first pass forms the prefix products of
+// the dx from the inputs alone and the second adds each pair once, in registers (ring3_pair_batch).
+// A lane's words of the parking area (word w at raw[w * S2K_RAW_WS]) during the construction -- W = 414 of the 32 x 27 are used, 612 are
+// written per ring (162 + 108 + 27 + 144 + 36 + 135):
 //     words   0..35   C, 3C, 18 words (x, y) each: on the chains' Z, then on D1
-//     words  36..179  Q_0..Q_7, 18 words each (written by the backward pass of stage 1)
-//     words 180..854  stage 2: pair k = 0..14, 45 words (x+, y+, x-, y-, product of the dx before it); pair 15 is never parked: the
-//                     forward pass hands it to the backward pass in registers, which is what makes 36 + 144 + 15 * 45 = 855 <= 864
-//     before stage 2 the same words hold: 180..251 T1, 3T1, T2, 3T2 (18 words each, rescaled), 300..479 the four pairs of stage 1,
-//     702..863 the three chains as ptab_build_raw_n parks them (6 slots of 27 words)
+//     words  36..179  Q_0..Q_7, 18 words each (written by the second pass of stage 1)
+//     words 180..314  stage 2: the product of the dx before pair k, k = 1..15, 9 words each at 180 + 9 (k - 1) (that of pair 0 is 1)
+//     before stage 2 the same words hold: 180..251 T1, 3T1, T2, 3T2 (18 words each, rescaled), 252..278 stage 1's three prefix products,
+//     and before stage 1 252..413 the three chains as ptab_build_raw_n parks them (6 slots of 27 words)
+//     words 414..863  unused by this form (the joint form, which shares the area's size, uses all 864)
 struct piece43 { u64 m; int neg; };
 #define S2K_R3_DIGITS 22
 #define S2K_R3_Q0 36
-#define S2K_R3_PAIR0 180
+#define S2K_R3_PROD0 180
 #define S2K_R3_T0 180
-#define S2K_R3_S1PAIR0 300
-#define S2K_R3_CHAIN0 702
-#define S2K_R3_PAIR_WORDS 45
+#define S2K_R3_S1PROD0 252
+#define S2K_R3_CHAIN0 252
+#define S2K_R3_PARK_WORDS 414                                   /* W: the highest used word + 1 */
+#ifndef S2K_R3_AHEAD
+#define S2K_R3_AHEAD 1
+#endif
 // out[0], out[1] = C pieces of k1, k2; out[2], out[3] = T1 pieces; out[4], out[5] = T2 pieces (sign of the half folded in)
 S2K_HD void sc_split_pieces3(piece43 out[6], const half_scalar& h0, const half_scalar& h1) {
     const u64 mask = (1ull << 43) - 1ull;
@@ -933,13 +939,15 @@ S2K_HD void ring3_recode(u32 dw[9], const piece43 pc[6]) {
     }
 }
 // One batch of N conjugate pairs P1 +- P2 (both affine on one curve: 18 parked words (x, y) each, pair k taking the words from w1(k) and
-// w2(k)): forward, both sums at Z = dx = x2 - x1 (5M + 3S the pair) parked at rec0 + 45 k with the product of the dx before them; backward,
-// every pair times the product of the OTHER dx -- all of them on Z = prod dx -- handed to out(k, x+, y+, x-, y-).  s: prod dx.
-// KEEP_LAST: pair N - 1 is not parked (rec0 .. rec0 + 45 (N - 1) - 1 is all that is written); it stays in registers between the passes.
+// w2(k)).  Both sums of a pair have Z = dx = x2 - x1, a difference of two parked inputs, so the prefix products need no addition:
+// pass 1, k = 0 .. N - 1: dx_k from the two x alone, the product p_k of the dx before it parked at prod0 + 9 (k - 1) (p_0 = 1 is not
+// parked), p <- p dx_k -- one product a trip, the next trip's x2 requested before it; pass 2, k = N - 1 .. 0: the pair is added ONCE
+// (5M + 3S), in registers, taken times p_k and the product of the dx behind it -- every pair on Z = prod dx -- and handed to out(k, r).
+// s: prod dx.  P1 stays in registers over the trips that share it (w1 changes once or twice a batch).  AHEAD (S2K_R3_AHEAD, default 1):
+// pass 2 also requests the next trip's x2, y2 and p_k before this trip's arithmetic -- 27 more live registers, which the kernel's 256
+// VGPRs hold without scratch; 0 leaves the loads at the head of their own trip (for A/B builds).
 struct ring3_pair { fe xp, yp, xm, ym, m, dx; };
-S2K_HD void ring3_pair_add(ring3_pair& r, const u32* raw, int w1o, int w2o) {
-    fe x1, y1, x2, y2;
-    rraw_load(x1, raw, w1o); rraw_load(y1, raw, w1o + 9); rraw_load(x2, raw, w2o); rraw_load(y2, raw, w2o + 9);
+S2K_HD void ring3_pair_add(ring3_pair& r, const fe& x1, const fe& y1, const fe& x2, const fe& y2) {
     fe dy, sy, t, c, d, d2, w1, w2, e, a1;
     fe_neg(t, x1, 1); fe_add2(r.dx, x2, t); fe_norm_weak(r.dx);
     fe_neg(t, y1, 1); fe_add2(dy, y2, t); fe_norm_weak(dy);
@@ -963,33 +971,42 @@ S2K_HD void ring3_pair_scale(ring3_pair& r, fe& s) {
     fe_mul2(r.xp, r.xp, m2, r.xm, r.xm, m2);                          // (4*1)
     fe_mul2(r.yp, r.yp, m3, r.ym, r.ym, m3);                          // (3*1)
 }
-template <int N, int KEEP_LAST, class W1, class W2, class Out>
-S2K_HD void ring3_pair_batch(fe& s, u32* raw, int rec0, W1 w1, W2 w2, Out out) {
-    ring3_pair r;
-    fe p; fe_set_int(p, 1);
+template <int N, int AHEAD, class W1, class W2, class Out>
+S2K_HD void ring3_pair_batch(fe& s, u32* raw, int prod0, W1 w1, W2 w2, Out out) {
+    {
+        fe p, x1, x2, nx; fe_set_int(p, 1);
+        rraw_load(x1, raw, w1(0)); rraw_load(x2, raw, w2(0));
 #pragma unroll 1
-    for (int k = 0; k < N - KEEP_LAST; k++) {
-        const int rec = rec0 + S2K_R3_PAIR_WORDS * k;
-        ring3_pair_add(r, raw, w1(k), w2(k));
-        rraw_store(raw, rec, r.xp); rraw_store(raw, rec + 9, r.yp); rraw_store(raw, rec + 18, r.xm); rraw_store(raw, rec + 27, r.ym);
-        rraw_store(raw, rec + 36, p);
-        fe_mul(p, p, r.dx);
+        for (int k = 0; k < N; k++) {
+            if (k + 1 < N) rraw_load(nx, raw, w2(k + 1));               // the next trip's x2, ahead of this trip's product
+            if (k > 0 && w1(k) != w1(k - 1)) rraw_load(x1, raw, w1(k));
+            fe dx, t;
+            fe_neg(t, x1, 1); fe_add2(dx, x2, t); fe_norm_weak(dx);
+            if (k > 0) rraw_store(raw, prod0 + 9 * (k - 1), p);
+            fe_mul(p, p, dx);
+            x2 = nx;
+        }
     }
     fe_set_int(s, 1);
-    if (KEEP_LAST) {
-        ring3_pair_add(r, raw, w1(N - 1), w2(N - 1));
-        r.m = p;
-        ring3_pair_scale(r, s);
-        out(N - 1, r);
-    }
+    ring3_pair r;
+    fe x1, y1, x2, y2, nx, ny, nm;
+    if (AHEAD) { rraw_load(x2, raw, w2(N - 1)); rraw_load(y2, raw, w2(N - 1) + 9); rraw_load(r.m, raw, prod0 + 9 * (N - 2)); }
 #pragma unroll 1
-    for (int k = N - 1 - KEEP_LAST; k >= 0; k--) {
-        const int rec = rec0 + S2K_R3_PAIR_WORDS * k;
-        rraw_load(r.xp, raw, rec); rraw_load(r.yp, raw, rec + 9); rraw_load(r.xm, raw, rec + 18); rraw_load(r.ym, raw, rec + 27); rraw_load(r.m, raw, rec + 36);
-        fe x1; rraw_load(x1, raw, w1(k)); rraw_load(r.dx, raw, w2(k));
-        fe_neg(x1, x1, 1); fe_add(r.dx, x1); fe_norm_weak(r.dx);
+    for (int k = N - 1; k >= 0; k--) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) S2K_OPAQUE(s.n[i]);                 // (carried around the 16-trip loop as it is, the compiler keeps s in register pairs and spends 390 more instructions a trip on s * dx)
+        if (k == N - 1 || w1(k) != w1(k + 1)) { rraw_load(x1, raw, w1(k)); rraw_load(y1, raw, w1(k) + 9); }
+        if (AHEAD) {
+            if (k > 0) { rraw_load(nx, raw, w2(k - 1)); rraw_load(ny, raw, w2(k - 1) + 9); }
+            if (k > 1) rraw_load(nm, raw, prod0 + 9 * (k - 2)); else fe_set_int(nm, 1);
+        } else {
+            rraw_load(x2, raw, w2(k)); rraw_load(y2, raw, w2(k) + 9);
+            if (k > 0) rraw_load(r.m, raw, prod0 + 9 * (k - 1)); else fe_set_int(r.m, 1);
+        }
+        ring3_pair_add(r, x1, y1, x2, y2);
         ring3_pair_scale(r, s);
         out(k, r);
+        if (AHEAD) { x2 = nx; y2 = ny; r.m = nm; }
     }
 }
 // C, T1 = 2^43*C, T2 = 2^86*C finite, magnitudes <= (5,3,1).  rtab: this lane's S2K_RTAB_WORDS; raw: this lane's column of its wavefront's
@@ -1019,7 +1036,7 @@ S2K_HD void ecmult_ring3_tables(u32* rtab, u32* raw, const gej& C, const gej& T1
     }
     fe d1, d2;
     // stage 1: pair k = 2 (b - 1)/2 + (c - 1)/2 : b*T1 +- c*T2  ->  Q_2k = b*T1 + c*T2, Q_2k+1 = b*T1 - c*T2
-    ring3_pair_batch<4, 0>(d1, raw, S2K_R3_S1PAIR0,
+    ring3_pair_batch<4, S2K_R3_AHEAD>(d1, raw, S2K_R3_S1PROD0,
         [](int k) { return S2K_R3_T0 + 18 * (k >> 1); }, [](int k) { return S2K_R3_T0 + 36 + 18 * (k & 1); },
         [&](int k, const ring3_pair& r) {
             const int q = S2K_R3_Q0 + 36 * k;
@@ -1035,7 +1052,7 @@ S2K_HD void ecmult_ring3_tables(u32* rtab, u32* raw, const gej& C, const gej& T1
         }
     }
     // stage 2: pair k = 8 (a - 1)/2 + q : a*C +- Q_q, normalised and packed, two sectors the pair
-    ring3_pair_batch<16, 1>(d2, raw, S2K_R3_PAIR0,
+    ring3_pair_batch<16, S2K_R3_AHEAD>(d2, raw, S2K_R3_PROD0,
         [](int k) { return 18 * (k >> 3); }, [](int k) { return S2K_R3_Q0 + 18 * (k & 7); },
         [&](int k, ring3_pair& r) {
             const int ai = k >> 3, bi = 2 + ((k >> 2) & 1), ca = (k >> 1) & 1, ci = (k & 1) ? 1 - ca : 2 + ca;      // (b + 3) / 2, (c + 3) / 2
