@@ -658,8 +658,9 @@ S2K_HD int ecmult_lane_split(gej& R, const gej& A, const gej& T, const scalar& n
 //     table can be twice as large as ecmult_lane_split's two: 32 sectors of 64 bytes;
 //   * no "key <- key + B", "T <- T + 2^64*B" updates between the steps;
 //   * + W (the table's number of windows) additions from H's table on the steps with j > 0.
-// What the rangeproof rings run is the three-base form further down (ecmult_ring3_tables / ecmult_ring3_step, S2K_RING_TRIPLE in rangeproof.h);
-// it shares the step body, the sizes and the digit-word layout with the joint form described here, which stays for A/B runs.
+// What the rangeproof rings run is the six-base form further down (ecmult_ring6_tables / ecmult_ring6_step, S2K_RING_SIX in rangeproof.h), over
+// the three bases of the three-base form (ecmult_ring3_tables / ecmult_ring3_step, S2K_RING_TRIPLE) and their lambda images; both share the
+// step body, the sizes and the digit-word layout with the joint form described here, and the two older forms stay for A/B runs.
 // The joint form (S2K_RING_JOINT = 1, the default): ONE table indexed by the digits of BOTH bases.  Its 32 sectors hold
 //     J(a, b) = a*C + b*T ,  a in {1, 3, 5, 7},  b in {+-1, +-3, +-5, +-7} ,  at sector ((a - 1) / 2) * 8 + (b + 7) / 2 ,
 // all on one Z, and a plain operand carries the digit of the C piece and the digit of the T piece of a GLV half at once (the lambda
@@ -971,8 +972,10 @@ S2K_HD void ring3_pair_scale(ring3_pair& r, fe& s) {
     fe_mul2(r.xp, r.xp, m2, r.xm, r.xm, m2);                          // (4*1)
     fe_mul2(r.yp, r.yp, m3, r.ym, r.ym, m3);                          // (3*1)
 }
-template <int N, int AHEAD, class W1, class W2, class Out>
-S2K_HD void ring3_pair_batch(fe& s, u32* raw, int prod0, W1 w1, W2 w2, Out out) {
+// ring3_pair_batch_xy: x2 of pair k at w2x(k) and y2 at w2y(k), which need not follow each other (the six-base form's P2 is a lambda
+// image: beta x parked once per point, y shared with the point itself); ring3_pair_batch: the 18-word form, y2 at w2(k) + 9.
+template <int N, int AHEAD, class W1, class W2X, class W2Y, class Out>
+S2K_HD void ring3_pair_batch_xy(fe& s, u32* raw, int prod0, W1 w1, W2X w2, W2Y w2y, Out out) {
     {
         fe p, x1, x2, nx; fe_set_int(p, 1);
         rraw_load(x1, raw, w1(0)); rraw_load(x2, raw, w2(0));
@@ -990,17 +993,17 @@ S2K_HD void ring3_pair_batch(fe& s, u32* raw, int prod0, W1 w1, W2 w2, Out out) 
     fe_set_int(s, 1);
     ring3_pair r;
     fe x1, y1, x2, y2, nx, ny, nm;
-    if (AHEAD) { rraw_load(x2, raw, w2(N - 1)); rraw_load(y2, raw, w2(N - 1) + 9); rraw_load(r.m, raw, prod0 + 9 * (N - 2)); }
+    if (AHEAD) { rraw_load(x2, raw, w2(N - 1)); rraw_load(y2, raw, w2y(N - 1)); rraw_load(r.m, raw, prod0 + 9 * (N - 2)); }
 #pragma unroll 1
     for (int k = N - 1; k >= 0; k--) {
 #pragma unroll
         for (int i = 0; i < 9; i++) S2K_OPAQUE(s.n[i]);                 // (carried around the 16-trip loop as it is, the compiler keeps s in register pairs and spends 390 more instructions a trip on s * dx)
         if (k == N - 1 || w1(k) != w1(k + 1)) { rraw_load(x1, raw, w1(k)); rraw_load(y1, raw, w1(k) + 9); }
         if (AHEAD) {
-            if (k > 0) { rraw_load(nx, raw, w2(k - 1)); rraw_load(ny, raw, w2(k - 1) + 9); }
+            if (k > 0) { rraw_load(nx, raw, w2(k - 1)); rraw_load(ny, raw, w2y(k - 1)); }
             if (k > 1) rraw_load(nm, raw, prod0 + 9 * (k - 2)); else fe_set_int(nm, 1);
         } else {
-            rraw_load(x2, raw, w2(k)); rraw_load(y2, raw, w2(k) + 9);
+            rraw_load(x2, raw, w2(k)); rraw_load(y2, raw, w2y(k));
             if (k > 0) rraw_load(r.m, raw, prod0 + 9 * (k - 1)); else fe_set_int(r.m, 1);
         }
         ring3_pair_add(r, x1, y1, x2, y2);
@@ -1008,6 +1011,11 @@ S2K_HD void ring3_pair_batch(fe& s, u32* raw, int prod0, W1 w1, W2 w2, Out out) 
         out(k, r);
         if (AHEAD) { x2 = nx; y2 = ny; r.m = nm; }
     }
+}
+template <int N, int AHEAD, class W1, class W2, class Out>
+S2K_HD void ring3_pair_batch(fe& s, u32* raw, int prod0, W1 w1, W2 w2, Out out) {
+    static_assert(N >= 2, "pass 2 requests the prefix product of pair N - 1 at prod0 + 9 (N - 2)");
+    ring3_pair_batch_xy<N, AHEAD>(s, raw, prod0, w1, w2, [w2](int k) { return w2(k) + 9; }, out);
 }
 // C, T1 = 2^43*C, T2 = 2^86*C finite, magnitudes <= (5,3,1).  rtab: this lane's S2K_RTAB_WORDS; raw: this lane's column of its wavefront's
 // parking area
@@ -1074,6 +1082,120 @@ S2K_HD void ecmult_ring3_tables(u32* rtab, u32* raw, const gej& C, const gej& T1
 #pragma unroll
     for (int i = 0; i < 9; i++) rtab[S2K_RTAB_ZISO + i] = ziso.n[i];
 }
+// ---- the six-base form of the ring table (S2K_RING_SIX, rangeproof.h) ------------------------------------------------------------
+// The same six pieces (sc_split_pieces3), but the lambda images of the three bases are bases of the table themselves: lambda*P is
+// (beta x, y) on the same Z, so they cost nothing to put IN, and one operand then carries one signed bit of every piece of BOTH GLV
+// halves.  A piece magnitude v is odd and below 2^43, so it is exactly 43 digits +-1: sum d_i 2^i = 2B - (2^43 - 1) with d_i = 2 b_i - 1,
+// i.e. b is read off B = (v - 1)/2 + 2^42 -- bit t of B is bit t + 1 of v, bit 42 is set -- and there is no fixed top digit.  Level i has
+// six signed digits (dC, d1, d2 of half 0; dC', d1', d2' of half 1) and takes
+//     dC * E(dC d1, dC d2, dC dC', dC d1', dC d2') ,   E(u, v, w0, w1, w2) = C + u*T1 + v*T2 + w0*lambda C + w1*lambda T1 + w2*lambda T2 ,
+// at sector (u < 0) + 2 (v < 0) + 4 (w0 < 0) + 8 (w1 < 0) + 16 (w2 < 0): again 32 sectors and the six-bit field neg << 5 | sector, field
+// `level` (0 = most significant) five per word, 43 fields in the same nine digit words.
+// A step is 43 levels of 1 doubling (none in front of the first) + 1 addition: 42 doublings, 43 operands the first of which is taken as
+// it is, and no beta product.
+// Construction (ecmult_ring6_tables): C and T1 brought to one Z (za z1 z2) in registers; the pair C +- T1 (Z = its dx, both sums parked);
+// T2, parked as it came meanwhile, onto that Z in one go (by za z1 dx); the two pairs (C +- T1) +- T2 brought to the product of their two dx, which gives the four
+//     A_a = C + u*T1 + v*T2 ,  a = (u < 0) + 2 (v < 0) ,
+// and beta x of each; then the sixteen conjugate pairs A_i +- lambda A_j (pair k = 4 i + j; P2 = (beta x_j, y_j)):
+// A_i + lambda A_j = E at sector i + 8 j, A_i - lambda A_j at that sector with bits 2..4 complemented; brought to the product of their
+// sixteen dx by prefix / suffix products and packed (ring3_pair_batch_xy).  The Z factor is za z1 z2 times all nineteen dx.  No dx can
+// vanish for a finite C (n would divide a small nonzero combination of 1, 2^43, 2^86 and their lambda multiples); one that does is a
+// factor of the Z factor all the same, and a step that finds the Z factor zero returns 0.
+// A lane's words of the parking area (word w at raw[w * S2K_RAW_WS]) during the construction -- W = 243 of the 32 x 27 are used, 324 are
+// written per ring (18 + 36 + 18 + 9 + 72 + 36 + 135):
+//     words   0..71   A_0..A_3, 18 words (x, y) each
+//     words  72..107  beta x of A_0..A_3, 9 words each
+//     words 108..242  the product of the dx before pair k, k = 1..15, 9 words each at 108 + 9 (k - 1) (that of pair 0 is 1)
+//     before the sixteen pairs the same words hold: 108..143 C + T1, C - T1 (18 words each), 144..161 T2 (as it came, then on their Z), 162..170 the dx of
+//     (C + T1) +- T2 (the one prefix product of that batch)
+//     words 243..863  unused by this form
+#define S2K_R6_LEVELS 43
+#define S2K_R6_BX0 72
+#define S2K_R6_PROD0 108
+#define S2K_R6_P0 108
+#define S2K_R6_T2 144
+#define S2K_R6_S1PROD0 162
+#define S2K_R6_PARK_WORDS 243                                   /* W: the highest used word + 1 */
+// bit b_i (digit d_i = 2 b_i - 1, i = 0 least significant) of an odd piece magnitude below 2^43
+S2K_HD u32 ring6_piece_bit(u64 m, int i) { return (u32)((((m >> 1) | (1ull << 42)) >> i) & 1ull); }
+// the digit words 0..8 of a step: field `level`, level 0 = most significant, five six-bit fields per word
+S2K_HD void ring6_recode(u32 dw[9], const piece43 pc[6]) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) dw[i] = 0;
+#pragma unroll
+    for (int pos = 0; pos < S2K_R6_LEVELS; pos++) {
+        const int i = S2K_R6_LEVELS - 1 - pos;
+        u32 sg[6];
+#pragma unroll
+        for (int t = 0; t < 6; t++) sg[t] = (ring6_piece_bit(pc[t].m, i) ^ 1u) ^ (u32)pc[t].neg;
+        const u32 v = sg[0] << 5 | (sg[2] ^ sg[0]) | (sg[4] ^ sg[0]) << 1 | (sg[1] ^ sg[0]) << 2 | (sg[3] ^ sg[0]) << 3 | (sg[5] ^ sg[0]) << 4;
+        dw[pos / 5] |= v << ((pos % 5) * 6);
+    }
+}
+// C, T1 = 2^43*C, T2 = 2^86*C finite, magnitudes <= (5,3,1).  rtab: this lane's S2K_RTAB_WORDS; raw: this lane's column of its wavefront's
+// parking area
+S2K_HD void ecmult_ring6_tables(u32* rtab, u32* raw, const gej& C, const gej& T1, const gej& T2) {
+    {   // C and T1 onto the Z  za * z1 * z2 , their pair, T2 onto the pair's Z; the Z so far waits in the Z factor's place
+        fe zoa, zo1, zo2, zs, x1, y1, x2, y2;
+        x2 = T2.x; y2 = T2.y; fe_norm_weak(x2); fe_norm_weak(y2);
+        rraw_store(raw, S2K_R6_T2, x2); rraw_store(raw, S2K_R6_T2 + 9, y2);     // (as it came, so that it is not live over the pair)
+        fe_mul2(zoa, T1.z, T2.z, zo1, C.z, T2.z);                   // each base by the product of the OTHER two's Z
+        fe_mul(zo2, C.z, T1.z);
+        {
+            fe m2, m3;
+            x1 = C.x; y1 = C.y; fe_norm_weak(x1); fe_norm_weak(y1);
+            fe_sqr(m2, zoa); fe_mul(m3, m2, zoa); fe_mul2(x1, x1, m2, y1, y1, m3);
+            x2 = T1.x; y2 = T1.y; fe_norm_weak(x2); fe_norm_weak(y2);
+            fe_sqr(m2, zo1); fe_mul(m3, m2, zo1); fe_mul2(x2, x2, m2, y2, y2, m3);
+        }
+        fe_mul(zs, zoa, C.z);
+        ring3_pair r;
+        ring3_pair_add(r, x1, y1, x2, y2);
+        fe_norm_weak(r.xp); fe_norm_weak(r.yp); fe_norm_weak(r.xm); fe_norm_weak(r.ym);
+        rraw_store(raw, S2K_R6_P0, r.xp); rraw_store(raw, S2K_R6_P0 + 9, r.yp); rraw_store(raw, S2K_R6_P0 + 18, r.xm); rraw_store(raw, S2K_R6_P0 + 27, r.ym);
+        fe_mul2(zs, zs, r.dx, zo2, zo2, r.dx);
+#pragma unroll
+        for (int i = 0; i < 9; i++) rtab[S2K_RTAB_ZISO + i] = zs.n[i];
+        {
+            fe m2, m3;
+            rraw_load(x2, raw, S2K_R6_T2); rraw_load(y2, raw, S2K_R6_T2 + 9);
+            fe_sqr(m2, zo2); fe_mul(m3, m2, zo2); fe_mul2(x2, x2, m2, y2, y2, m3);
+            rraw_store(raw, S2K_R6_T2, x2); rraw_store(raw, S2K_R6_T2 + 9, y2);
+        }
+    }
+    fe d1, d2;
+    // pair k: (C + T1) +- T2 (k = 0), (C - T1) +- T2 (k = 1)  ->  A_k (the sum), A_k+2 (the difference), and beta x of both
+    ring3_pair_batch<2, S2K_R3_AHEAD>(d1, raw, S2K_R6_S1PROD0,
+        [](int k) { return S2K_R6_P0 + 18 * k; }, [](int) { return S2K_R6_T2; },
+        [&](int k, const ring3_pair& r) {
+            fe beta, bp, bm; fe_set_beta(beta);
+            fe_mul2(bp, r.xp, beta, bm, r.xm, beta);
+            rraw_store(raw, 18 * k, r.xp); rraw_store(raw, 18 * k + 9, r.yp); rraw_store(raw, 18 * (k + 2), r.xm); rraw_store(raw, 18 * (k + 2) + 9, r.ym);
+            rraw_store(raw, S2K_R6_BX0 + 9 * k, bp); rraw_store(raw, S2K_R6_BX0 + 9 * (k + 2), bm);
+        });
+    // pair k = 4 i + j : A_i +- lambda A_j, normalised and packed, two sectors the pair
+    ring3_pair_batch_xy<16, S2K_R3_AHEAD>(d2, raw, S2K_R6_PROD0,
+        [](int k) { return 18 * (k >> 2); }, [](int k) { return S2K_R6_BX0 + 9 * (k & 3); }, [](int k) { return 18 * (k & 3) + 9; },
+        [&](int k, ring3_pair& r) {
+            const int sp = (k >> 2) | ((k & 3) << 3);
+            fe_normalize(r.xp); fe_normalize(r.yp); fe_normalize(r.xm); fe_normalize(r.ym);
+            u32* const ep = rtab + sp * 16;                                       // A_i + lambda A_j
+            u32* const em = rtab + (sp ^ 28) * 16;                                // A_i - lambda A_j
+            u32 wx[8], wy[8];
+            fe_to_words(wx, r.xp); fe_to_words(wy, r.yp);
+#pragma unroll
+            for (int i = 0; i < 8; i++) { ep[i] = wx[i]; ep[8 + i] = wy[i]; }
+            fe_to_words(wx, r.xm); fe_to_words(wy, r.ym);
+#pragma unroll
+            for (int i = 0; i < 8; i++) { em[i] = wx[i]; em[8 + i] = wy[i]; }
+        });
+    fe ziso;
+#pragma unroll
+    for (int i = 0; i < 9; i++) ziso.n[i] = rtab[S2K_RTAB_ZISO + i];
+    fe_mul(d1, d1, d2); fe_mul(ziso, ziso, d1);                               // (a dx of zero makes the Z factor zero: the step then returns 0)
+#pragma unroll
+    for (int i = 0; i < 9; i++) rtab[S2K_RTAB_ZISO + i] = ziso.n[i];
+}
 // e != 0; has_f uniform over the wavefront.  htab: this lane's generator's table (same layout as gtab).
 // the digit words 0..8 of a step of the two-base forms from the GLV halves (joint form: ring_joint_recode; separate form: 5-bit digits
 // (pos * 4 + stream), six per word, and the streams' signs in sneg)
@@ -1099,18 +1221,22 @@ S2K_HD void ring_step_recode(u32 dw[9], u32& sneg, const half_scalar& h0, const 
     }
 #endif
 }
-// TRIPLE = 1: the three-base form (above): 2 doublings a level and its own recoding; the fields sit where the joint form's do.
-template <int TRIPLE>
+// FORM = 1: the three-base form (above): 2 doublings a level and its own recoding; the fields sit where the joint form's do.
+// FORM = 2: the six-base form: 1 doubling a level, one operand a level (field `level`), no lambda operand.
+template <int FORM>
 S2K_HD int ecmult_ring_step_t(gej& R, const u32* rtab, const scalar& e, const scalar& s, const scalar& f, int has_f, const u32* gtab, const u32* htab,
                               const s2k_lds_ptr dig) {
-    constexpr int RING_W = TRIPLE ? 2 : S2K_RING_W, RING_GROUP = TRIPLE ? 2 : S2K_RING_GROUP, RING_ADDS_P = TRIPLE ? 2 * S2K_R3_DIGITS : S2K_RING_ADDS_P;
-    constexpr bool FIELDS = TRIPLE || S2K_RING_JOINT;           // six-bit fields neg << 5 | sector in the digit words
+    constexpr bool TRIPLE = FORM == 1, SIX = FORM == 2;
+    constexpr int RING_W = TRIPLE ? 2 : S2K_RING_W, RING_GROUP = TRIPLE ? 2 : S2K_RING_GROUP;
+    constexpr int RING_ADDS_P = SIX ? S2K_R6_LEVELS : TRIPLE ? 2 * S2K_R3_DIGITS : S2K_RING_ADDS_P;
+    constexpr bool FIELDS = FORM || S2K_RING_JOINT;           // six-bit fields neg << 5 | sector in the digit words
     u32 sneg = 0; (void)sneg;                                   // (separate form only)
     S2K_PROF_DECL;
     {
         half_scalar h0, h1; sc_split_lambda_odd(h0, h1, e);
         u32 dw[9];
-        if constexpr (TRIPLE) { piece43 pc3[6]; sc_split_pieces3(pc3, h0, h1); ring3_recode(dw, pc3); }
+        if constexpr (SIX) { piece43 pc3[6]; sc_split_pieces3(pc3, h0, h1); ring6_recode(dw, pc3); }
+        else if constexpr (TRIPLE) { piece43 pc3[6]; sc_split_pieces3(pc3, h0, h1); ring3_recode(dw, pc3); }
         else ring_step_recode(dw, sneg, h0, h1);
 #pragma unroll
         for (int i = 0; i < 9; i++) dig[i * S2K_DIG_STRIDE] = dw[i];
@@ -1126,7 +1252,7 @@ S2K_HD int ecmult_ring_step_t(gej& R, const u32* rtab, const scalar& e, const sc
         addr = rtab; valid = 0; neg = 0;
         if (idx < a_g0) {
             if constexpr (FIELDS) {
-                const u32 v = (dig[(idx / 5) * S2K_DIG_STRIDE] >> ((idx % 5) * 6)) & 63u;   // ring_joint_field / ring3_field
+                const u32 v = (dig[(idx / 5) * S2K_DIG_STRIDE] >> ((idx % 5) * 6)) & 63u;   // ring_joint_field / ring3_field / ring6_recode
                 valid = 1;
                 neg = (int)(v >> 5);
                 addr = rtab + (v & 31u) * 16;
@@ -1161,8 +1287,28 @@ S2K_HD int ecmult_ring_step_t(gej& R, const u32* rtab, const scalar& e, const sc
     op_locate(nxt_addr, nxt_valid, nxt_neg, 1);
     // variable part, separate form: additions 0..51 as 26 (plain stream, lambda stream) pairs, 5 doublings in front of every group of four
     // but the first; joint form: additions 0..43 as 22 such pairs, one per level, 3 doublings in front of every pair but the first (three-base
-    // form: 2 doublings)
+    // form: 2 doublings); six-base form: additions 0..42, one per level, 1 doubling in front of every one but the first
     int au = 0;
+    if constexpr (SIX) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) raw[k] = nxt_addr[k];
+        gej_set_ge(R, cur);                                                 // level 0: the operand as it is
+        au = 1;
+        op_decode(cur, raw, nxt_neg, 0); cur_valid = nxt_valid;
+        op_locate(nxt_addr, nxt_valid, nxt_neg, 2);
+#pragma unroll 1
+        while (au < a_g0) {
+            S2K_PROF_MARK(7);
+            gej_double_lean(R, R);
+            S2K_PROF_MARK(6);
+#pragma unroll
+            for (int k = 0; k < 16; k++) raw[k] = nxt_addr[k];              // request the next record before the arithmetic
+            { const int same_x = gej_add_ge_lean(R, R, cur); if (S2K_WAVE_ANY(same_x)) return 0; }
+            au++;
+            op_decode(cur, raw, nxt_neg, 0); cur_valid = nxt_valid;
+            op_locate(nxt_addr, nxt_valid, nxt_neg, au + 1);
+        }
+    } else
     while (au < a_g0) {
         if (au >= RING_GROUP && !(au & (RING_GROUP - 1))) {
             S2K_PROF_MARK(7);
@@ -1244,6 +1390,10 @@ S2K_HD int ecmult_ring_step(gej& R, const u32* rtab, const scalar& e, const scal
 S2K_HD int ecmult_ring3_step(gej& R, const u32* rtab, const scalar& e, const scalar& s, const scalar& f, int has_f, const u32* gtab, const u32* htab,
                              const s2k_lds_ptr dig) {
     return ecmult_ring_step_t<1>(R, rtab, e, s, f, has_f, gtab, htab, dig);
+}
+S2K_HD int ecmult_ring6_step(gej& R, const u32* rtab, const scalar& e, const scalar& s, const scalar& f, int has_f, const u32* gtab, const u32* htab,
+                             const s2k_lds_ptr dig) {
+    return ecmult_ring_step_t<2>(R, rtab, e, s, f, has_f, gtab, htab, dig);
 }
 
 

@@ -803,3 +803,5 @@ extern "C" __attribute__((visibility("default"))) int s2k_prof_read(unsigned lon
 #endif
 // which ring table k_rp_rings_shared was built with: 1 = three bases (S2K_RING_TRIPLE, rangeproof.h), 0 = the joint table of two
 extern "C" __attribute__((visibility("default"))) int s2k_ring_triple(void) { return S2K_RING_TRIPLE; }
+// 1 = that table also holds the lambda images of the three bases (S2K_RING_SIX, rangeproof.h), one operand a level
+extern "C" __attribute__((visibility("default"))) int s2k_ring_six(void) { return S2K_RING_TRIPLE && S2K_RING_SIX; }

@@ -533,8 +533,18 @@ S2K_HD int rp_ring_suspect(const gej& C, const u32* xmul /* this (exp, ring)'s 3
 #ifndef S2K_RING_TRIPLE
 #define S2K_RING_TRIPLE 1
 #endif
-#if S2K_RING_TRIPLE
+// S2K_RING_SIX (inside S2K_RING_TRIPLE: the same three bases and chain): the table over C, 2^43 C, 2^86 C AND their lambda images, one signed
+// bit of each per operand (ecmult.h: ecmult_ring6_tables, 43 levels of 1 doubling + 1 addition, no beta product in a step); 0 = the
+// three-base form, for A/B runs.  Measured on MI355X (profiles/ring_six_bench_ab.txt): headline +4.9 %, above the three-base form in all five pairs.
+#ifndef S2K_RING_SIX
+#define S2K_RING_SIX 1
+#endif
+#if S2K_RING_TRIPLE && S2K_RING_SIX
+#define S2K_RP_RING_STEP ecmult_ring6_step
+#define S2K_RP_RING3_TABLES ecmult_ring6_tables
+#elif S2K_RING_TRIPLE
 #define S2K_RP_RING_STEP ecmult_ring3_step
+#define S2K_RP_RING3_TABLES ecmult_ring3_tables
 #else
 #define S2K_RP_RING_STEP ecmult_ring_step
 #endif
@@ -601,7 +611,7 @@ S2K_HD int rp_rings_shared(const rp_rec& rec, const u32* pub28, unsigned char* r
             if (h == 0) T1 = T;
         }
         S2K_PROF_MARK(11);
-        if (!(dbg & 2u)) ecmult_ring3_tables(M.rtab + (size_t)q * S2K_RTAB_WORDS, M.raw, C, T1, T);
+        if (!(dbg & 2u)) S2K_RP_RING3_TABLES(M.rtab + (size_t)q * S2K_RTAB_WORDS, M.raw, C, T1, T);
 #else
 #pragma unroll 1
         for (int k = 0; k < ((dbg & 1u) ? 0 : 64); k++) gej_double_lean(T, T);

@@ -31,8 +31,10 @@ names = ["step prologue (key load, next key, T update)", "ecmult: split + digits
          "hash + bookkeeping", "main loop: 4 lean doublings", "main loop: lean addition + operand decode/locate", "split: 2 x co-Z table construction",
          "split: 2 x table rescale", "split: generator additions + leaving the isomorphic curve", "ring: 2^64 * key chain (64 doublings)"]
 if os.environ.get("S2K_GEN_CACHE", "") != "0":        # the shared-generator form of the kernel (rp_ring_shared / ecmult_ring_step) uses the slots like this
-    names = ["step prologue (scalars, f_j)", "ring step: split + digits", "-", "-", "to-affine (inversion)", "hash + bookkeeping", "ring step: lean doublings (21 x 2, three-base table; 21 x 3 with -DS2K_RING_TRIPLE=0, the joint table)",
-             "ring step: lean additions + operand decode/locate (variable point)", "ring: the 32-sector table (three bases C, 2^43 C, 2^86 C; the joint table of C and 2^64 C with -DS2K_RING_TRIPLE=0)", "-",
+    names = ["step prologue (scalars, f_j)", "ring step: split + digits", "-", "-", "to-affine (inversion)", "hash + bookkeeping",
+             "ring step: lean doublings (42 x 1, six-base table; 21 x 2 with -DS2K_RING_SIX=0, the three-base table; 21 x 3 with -DS2K_RING_TRIPLE=0, the joint table)",
+             "ring step: lean additions + operand decode/locate (variable point; one operand a level with the six-base table, two with the others)",
+             "ring: the 32-sector table (six bases: C, 2^43 C, 2^86 C and their lambda images; the three without the images with -DS2K_RING_SIX=0; the joint table of C and 2^64 C with -DS2K_RING_TRIPLE=0)", "-",
              "ring step: G and H table additions + leaving the isomorphic curve", "ring: chain to 2^43 * C and 2^86 * C (86 doublings; to 2^64 * C, 64 doublings, with -DS2K_RING_TRIPLE=0)"]
 tot = v[:12].sum()
 steps = n * 32 * 4 / 64
