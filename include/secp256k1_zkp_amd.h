@@ -74,6 +74,8 @@ S2K_API void s2k_clear_status(void);
  *   s2k_ecmult_multi_partial_dev run a sum with more terms than this as consecutive launches over slices of the term arrays and add the
  *   partial sums -- the reference's own treatment of a sum that exceeds its scratch space (src/ecmult_impl.h:804-820, :856-865).  The
  *   result does not depend on the value; tests lower it to walk the loop at small sizes.
+ * S2K_OPT_MUSIG_SUM_FANIN (default 64, 2..64): how many partial points one lane of the MuSig2 summing kernel folds per pass (key and nonce
+ *   aggregation).  Results never depend on it; tests lower it to walk the multi-pass loop at small set sizes.
  * S2K_OPT_GTAB_BITS (20, 22, 24 or 26; default 26, $S2K_GTAB_BITS): digit width of the device's fixed-base tables (G and the rangeproof generator
  *   slots: 0.44 / 1.6 / 5.9 / 21.5 GB each, one more addition per fixed-base multiplication for every step down).  Changing it gives the device's
  *   tables back (after a device-wide wait: an administrative call) and the next call that needs one builds it at the new width; a width that
@@ -91,6 +93,7 @@ S2K_API void s2k_clear_status(void);
 #define S2K_OPT_SYNC_SPLIT 9
 #define S2K_OPT_MSM_MAX_TERMS 10
 #define S2K_OPT_GTAB_BITS 11
+#define S2K_OPT_MUSIG_SUM_FANIN 12
 S2K_API int s2k_engine_set_option(s2k_engine* e, int option, long value);
 /* Rangeproof generator tables.  The four public keys of a Borromean ring differ by multiples of the proof's generator
  * (secp256k1_rangeproof_pub_expand, src/modules/rangeproof/rangeproof_impl.h:19-51), so when the engine holds a fixed-base table of that
@@ -264,8 +267,8 @@ S2K_API int secp256k1_ecdsa_adaptor_verify_batch_dev(s2k_engine* e, void* stream
  * device memory.  DIFFERENCE FROM THE REFERENCE: where results[i] == 0 the session is 133 zero bytes; the reference leaves the
  * object untouched there (and calls the illegal-argument callback on a wrong magic or an all-zero adaptor object).
  *
- * Out of scope, with the reference: everything that touches a secret (nonce_gen*, partial_sign, adapt, extract_adaptor);
- * pubkey_agg and the cache tweaks (once per key set); nonce_agg and partial_sig_agg (a few additions each). */
+ * Out of scope, with the reference: everything that touches a secret (nonce_gen*, partial_sign, adapt, extract_adaptor).  Key
+ * aggregation, the cache tweaks, nonce aggregation and signature aggregation are the next section. */
 S2K_API int secp256k1_musig_partial_sig_verify_batch(s2k_engine* e, int32_t* results, const unsigned char* partial_sigs, int sig_format,
                                                      const unsigned char* pubnonces, int nonce_format, const unsigned char* pubkeys, int pk_format,
                                                      const unsigned char* keyagg_caches197, const unsigned char* sessions133, size_t n_sessions,
@@ -280,6 +283,67 @@ S2K_API int secp256k1_musig_nonce_process_batch(s2k_engine* e, int32_t* results,
 S2K_API int secp256k1_musig_nonce_process_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* sessions_out133, const unsigned char* aggnonces,
                                                     int nonce_format, const unsigned char* msgs32, const unsigned char* keyagg_caches197,
                                                     const unsigned char* adaptors64, size_t n);
+
+/* ---- MuSig2: key aggregation, cache tweaks, nonce aggregation, signature aggregation (the rest of the coordinator's flow) -----
+ * With the two calls above a signing round stays on the device: keys -> cache -> tweaked cache -> aggregate nonce -> session ->
+ * share verdicts -> final BIP-340 signature (which secp256k1_schnorrsig_verify_batch_dev can check on the spot).  All public data.
+ * Conventions as above: results[] per item; 0 and zeroed outputs for a refused item, neighbours never affected;
+ * S2K_STATUS_ILLEGAL_ARGUMENT only for NULL arguments, out-of-range formats and offsets that do not start at 0 or that decrease.  In
+ * the _dev forms every byte array is in HBM, outputs and results are zeroed on the stream first, and the offset arrays are HOST
+ * arrays of n + 1 entries, read before the call returns (as offsets_host of s2k_ecmult_multi_many_dev).
+ *
+ * results[k] = secp256k1_musig_pubkey_agg(ctx, agg_pks_out64 + 64 k, caches_out197 + 197 k, keys of set k, set_off[k+1] - set_off[k])
+ *                                       (src/modules/musig/keyagg_impl.h:156-215)
+ * pubkeys        the keys of all sets, one after the other; set k owns keys [set_off[k], set_off[k+1]).  pk_format as in the ECDSA
+ *                calls (0: 33 bytes each, 1: 64-byte `secp256k1_pubkey` objects, 2: 65 bytes uncompressed or hybrid).
+ * caches_out197  byte for byte `secp256k1_musig_keyagg_cache`: magic | pk | second_pk (64 zero bytes when every key equals the first)
+ *                | pks_hash | parity_acc 0 | tweak 0.  agg_pks_out64 (may be NULL): the `secp256k1_xonly_pubkey` object (even y).
+ * The second key is the first key that differs from key 0: format 1 compares the 64 bytes (the reference's memcmp), format 0 the 33
+ * bytes, format 2 bytes 1..64, so that a hybrid encoding of key 0's point is NOT a second key.
+ * results[k] == 0 with zeroed outputs: an empty set (the reference: ARG_CHECK(n_pubkeys > 0)); a set with a key that does not parse
+ * or an all-zero-x object; DIFFERENCE FROM THE REFERENCE: an aggregate at infinity, which no hash reaches and the reference only
+ * guards with a VERIFY_CHECK.
+ *
+ * results[i] = xonly[i] ? secp256k1_musig_pubkey_xonly_tweak_add(ctx, pubkeys_out64 + 64 i, cache_i, tweaks32 + 32 i)
+ *                       : secp256k1_musig_pubkey_ec_tweak_add(...)        (keyagg_impl.h:231-273)
+ * xonly NULL: every item is a plain tweak; a byte other than 0 or 1 gives 0.  caches_out197 may be the very buffer caches_in197 (the
+ * reference works in place); any other overlap is not supported.  pubkeys_out64 (may be NULL): `secp256k1_pubkey` objects.
+ * A host-form call that fails as a whole (return 0) leaves zeroed outputs, except the caches of an in-place call, which are its input.
+ * results[i] == 0: a wrong cache magic, a tweak >= the group order, a result at infinity.  DIFFERENCE FROM THE REFERENCE: the output
+ * cache is then 197 zero bytes; the reference leaves the cache as it was.
+ *
+ * results[k] = pubnonces parse && secp256k1_musig_nonce_agg(ctx, aggnonce_k, pubnonces of session k, nonce_off[k+1] - nonce_off[k])
+ *                                       (session_impl.h:493-531)
+ * pubnonces      nonce_format 0: 66 bytes each as secp256k1_musig_pubnonce_parse reads them; 1: 132-byte objects.
+ * aggnonces_out  out_format 0: 66 bytes each as secp256k1_musig_aggnonce_serialize writes them; 1: 132-byte `secp256k1_musig_aggnonce`
+ *                objects.  An infinite sum is a valid result: 33 zero bytes serialised, 64 zero bytes inside the object.
+ * results[k] == 0 with zeroed output: an empty range, a wrong pubnonce magic, a serialised pubnonce the parser refuses (33 zero bytes
+ * included).
+ *
+ * results[k] = shares parse && secp256k1_musig_partial_sig_agg(ctx, sigs64_out + 64 k, session_k, shares of session k, ...)
+ *                                       (session_impl.h:779-805)
+ * sigs64_out     fin_nonce | (s_part + sum of s_i) mod n: the BIP-340 signature.  partial_sigs: sig_format as in the verifier.
+ * results[k] == 0 with 64 zero bytes: an empty range, a wrong session or signature magic, a serialised s >= n (an object holding
+ * s = n is reduced, not refused, as in the verifier).
+ *
+ * Out of scope: group forms of these four calls, the hook into the reference's own functions (integration/), pubkey_get (bytes 4..67
+ * of the cache are the key) and BIP-328 derivation; and, as above, everything that touches a secret. */
+S2K_API int secp256k1_musig_pubkey_agg_batch(s2k_engine* e, int32_t* results, unsigned char* caches_out197, unsigned char* agg_pks_out64, const unsigned char* pubkeys,
+                                             int pk_format, const uint64_t* set_off, size_t n_sets);
+S2K_API int secp256k1_musig_pubkey_agg_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* caches_out197, unsigned char* agg_pks_out64,
+                                                 const unsigned char* pubkeys, int pk_format, const uint64_t* set_off, size_t n_sets);
+S2K_API int secp256k1_musig_pubkey_tweak_add_batch(s2k_engine* e, int32_t* results, unsigned char* caches_out197, unsigned char* pubkeys_out64,
+                                                   const unsigned char* caches_in197, const unsigned char* tweaks32, const unsigned char* xonly, size_t n);
+S2K_API int secp256k1_musig_pubkey_tweak_add_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* caches_out197, unsigned char* pubkeys_out64,
+                                                       const unsigned char* caches_in197, const unsigned char* tweaks32, const unsigned char* xonly, size_t n);
+S2K_API int secp256k1_musig_nonce_agg_batch(s2k_engine* e, int32_t* results, unsigned char* aggnonces_out, int out_format, const unsigned char* pubnonces,
+                                            int nonce_format, const uint64_t* nonce_off, size_t n_sessions);
+S2K_API int secp256k1_musig_nonce_agg_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* aggnonces_out, int out_format,
+                                                const unsigned char* pubnonces, int nonce_format, const uint64_t* nonce_off, size_t n_sessions);
+S2K_API int secp256k1_musig_partial_sig_agg_batch(s2k_engine* e, int32_t* results, unsigned char* sigs64_out, const unsigned char* sessions133,
+                                                  const unsigned char* partial_sigs, int sig_format, const uint64_t* sig_off, size_t n_sessions);
+S2K_API int secp256k1_musig_partial_sig_agg_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* sigs64_out, const unsigned char* sessions133,
+                                                      const unsigned char* partial_sigs, int sig_format, const uint64_t* sig_off, size_t n_sessions);
 
 /* ---- Whitelist-signature batch verification -------------------------------------------------------------------------
  * results[i] = secp256k1_whitelist_signature_parse(ctx, &sig, sigs + sig_off[i], sig_off[i+1] - sig_off[i]) &&
@@ -475,6 +539,10 @@ S2K_API int secp256k1_ecdsa_adaptor_verify_amd(const void* ctx, const unsigned c
  * all five point at the reference's objects (36, 132, 64, 197 and 133 bytes). */
 S2K_API int secp256k1_musig_partial_sig_verify_amd(const void* ctx, const void* partial_sig, const void* pubnonce, const void* pubkey, const void* keyagg_cache,
                                                    const void* session);
+/*   secp256k1_musig_pubkey_agg(ctx, agg_pk, keyagg_cache, pubkeys, n_pubkeys)          include/secp256k1_musig.h,
+ *                                                                                      src/modules/musig/keyagg_impl.h:156
+ * pubkeys: n_pubkeys pointers to 64-byte secp256k1_pubkey objects; agg_pk (64 bytes) and keyagg_cache (197 bytes) may each be NULL. */
+S2K_API int secp256k1_musig_pubkey_agg_amd(const void* ctx, void* agg_pk, void* keyagg_cache, const void* const* pubkeys, size_t n_pubkeys);
 /*   secp256k1_whitelist_verify(ctx, sig, online_pubkeys, offline_pubkeys, n_keys, sub_pubkey)      include/secp256k1_whitelist.h
  * sig: the secp256k1_whitelist_signature object {size_t n_keys; unsigned char data[32 * 256]}; the key arrays: n_keys 64-byte
  * secp256k1_pubkey objects each (they may be NULL when n_keys is 0 here; the reference's ARG_CHECK refuses that). */

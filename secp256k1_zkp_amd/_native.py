@@ -54,6 +54,14 @@ SIGNATURES = {
     "secp256k1_musig_partial_sig_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _c.c_int, _vp, _c.c_int, _vp, _vp, _sz, _vp, _sz]),
     "secp256k1_musig_nonce_process_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _vp, _sz]),
     "secp256k1_musig_nonce_process_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _vp, _sz]),
+    "secp256k1_musig_pubkey_agg_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_musig_pubkey_agg_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_musig_pubkey_tweak_add_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_musig_pubkey_tweak_add_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_musig_nonce_agg_batch": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_musig_nonce_agg_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_musig_partial_sig_agg_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_musig_partial_sig_agg_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "secp256k1_xonly_pubkey_tweak_add_check_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "secp256k1_xonly_pubkey_tweak_add_check_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "secp256k1_pubkey_tweak_add_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
@@ -83,6 +91,7 @@ SIGNATURES = {
     "secp256k1_ecdsa_recover_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "secp256k1_ecdsa_adaptor_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "secp256k1_musig_partial_sig_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "secp256k1_musig_pubkey_agg_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _sz]),
     "secp256k1_whitelist_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _vp]),
     "secp256k1_xonly_pubkey_tweak_add_check_amd": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _vp]),
     "secp256k1_xonly_pubkey_tweak_add_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),

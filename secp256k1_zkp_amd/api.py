@@ -159,6 +159,7 @@ class Engine:
     OPT_SYNC_SPLIT = 9
     OPT_MSM_MAX_TERMS = 10
     OPT_GTAB_BITS = 11
+    OPT_MUSIG_SUM_FANIN = 12
 
     def cache_generator(self, gen64):
         """Build the fixed-base table of one rangeproof generator now (s2k_engine_cache_generator)."""
@@ -372,6 +373,105 @@ class Engine:
         n = msgs32.numel() // 32 if n is None else n
         self._check(self._lib.secp256k1_musig_nonce_process_batch_dev(self._h, stream, _dp(results), _dp(sessions_out), _dp(aggnonces), nonce_format, _dp(msgs32),
                                                                       _dp(keyagg_caches), _dp(adaptors), n), "secp256k1_musig_nonce_process_batch_dev")
+
+    # ---- secp256k1_musig_pubkey_agg, the cache tweaks, secp256k1_musig_nonce_agg and secp256k1_musig_partial_sig_agg (keyagg_impl.h:156-273, session_impl.h:512-531, :779-805), batched ----
+    @staticmethod
+    def _musig_off(what, off, item_bytes, data):
+        """offsets (n + 1 entries, counted in items) as a uint64 host array, checked against the data array"""
+        if off is None:
+            raise ValueError(f"{what}: missing offsets")
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError(f"{what}: offsets need n + 1 entries")
+        o = off.astype(np.int64)
+        if int(o[0]) != 0 or (np.diff(o) < 0).any():
+            raise ValueError(f"{what}: offsets must start at 0 and never decrease")
+        if data is not None:
+            _need(what, data, item_bytes * int(o[-1]))
+        return off
+
+    def musig_pubkey_agg(self, pubkeys, set_off, pk_format=0, want_agg_pk=True):
+        """pubkeys: the keys of all sets, concatenated (pk_format 0: 33 bytes each, 1: 64-byte objects, 2: 65 bytes); set k owns keys
+        [set_off[k], set_off[k+1]).  Returns (verdicts, n_sets*197 cache bytes, n_sets*64 x-only key objects or None); the outputs of a
+        refused set (empty, a key that does not parse, an aggregate at infinity) are all zero."""
+        if pk_format not in _ECDSA_PK_BYTES:
+            raise ValueError("musig_pubkey_agg: pk_format must be 0, 1 or 2")
+        if pubkeys is None:
+            raise ValueError("musig_pubkey_agg: missing array")
+        pubkeys = _u8(pubkeys)
+        set_off = self._musig_off("musig_pubkey_agg", set_off, _ECDSA_PK_BYTES[pk_format], pubkeys)
+        n = set_off.size - 1
+        res = np.zeros(n, np.int32); caches = np.zeros(197 * n, np.uint8); agg = np.zeros(64 * n, np.uint8) if want_agg_pk else None
+        self._check(self._lib.secp256k1_musig_pubkey_agg_batch(self._h, _p(res), _p(caches), _p(agg), _p(pubkeys), pk_format, _p(set_off), n), "secp256k1_musig_pubkey_agg_batch")
+        return res, caches, agg
+
+    def musig_pubkey_agg_dev(self, results, caches_out, agg_pks_out, pubkeys, set_off, pk_format=0, stream=None):
+        """byte arrays in HBM (torch tensors; agg_pks_out may be None); set_off is a HOST array of n_sets + 1 key counts, read before the call returns"""
+        set_off = self._musig_off("musig_pubkey_agg_dev", set_off, 0, None)
+        self._check(self._lib.secp256k1_musig_pubkey_agg_batch_dev(self._h, stream, _dp(results), _dp(caches_out), _dp(agg_pks_out), _dp(pubkeys), pk_format, _p(set_off),
+                                                                   set_off.size - 1), "secp256k1_musig_pubkey_agg_batch_dev")
+
+    def musig_pubkey_tweak_add(self, keyagg_caches, tweaks32, xonly=None, want_pubkeys=True):
+        """keyagg_caches n*197; tweaks32 n*32; xonly None (all plain tweaks) or one byte per item (1: x-only, 0: plain; anything else is
+        refused).  Returns (verdicts, n*197 new cache bytes, n*64 secp256k1_pubkey objects or None); a refused item's outputs are all zero."""
+        if keyagg_caches is None or tweaks32 is None:
+            raise ValueError("musig_pubkey_tweak_add: missing array")
+        keyagg_caches = _u8(keyagg_caches); tweaks32 = _u8(tweaks32); n = tweaks32.size // 32
+        _need("musig_pubkey_tweak_add keyagg_caches", keyagg_caches, 197 * n); _need("musig_pubkey_tweak_add tweaks32", tweaks32, 32 * n)
+        if xonly is not None:
+            xonly = _u8(xonly); _need("musig_pubkey_tweak_add xonly", xonly, n)
+        res = np.zeros(n, np.int32); out = np.zeros(197 * n, np.uint8); pks = np.zeros(64 * n, np.uint8) if want_pubkeys else None
+        self._check(self._lib.secp256k1_musig_pubkey_tweak_add_batch(self._h, _p(res), _p(out), _p(pks), _p(keyagg_caches), _p(tweaks32), _p(xonly), n),
+                    "secp256k1_musig_pubkey_tweak_add_batch")
+        return res, out, pks
+
+    def musig_pubkey_tweak_add_dev(self, results, caches_out, pubkeys_out, caches_in, tweaks32, xonly=None, n=None, stream=None):
+        """every array in HBM (torch tensors); caches_out may be caches_in; pubkeys_out and xonly may be None"""
+        n = tweaks32.numel() // 32 if n is None else n
+        self._check(self._lib.secp256k1_musig_pubkey_tweak_add_batch_dev(self._h, stream, _dp(results), _dp(caches_out), _dp(pubkeys_out), _dp(caches_in), _dp(tweaks32),
+                                                                         _dp(xonly), n), "secp256k1_musig_pubkey_tweak_add_batch_dev")
+
+    def musig_nonce_agg(self, pubnonces, nonce_off, nonce_format=0, out_format=0):
+        """pubnonces: 66 bytes serialised or 132-byte objects each, all sessions concatenated; session k owns [nonce_off[k], nonce_off[k+1]).
+        Returns (verdicts, aggregate nonces: 66 bytes serialised or 132-byte objects each, all zero where the verdict is 0)."""
+        if nonce_format not in (0, 1) or out_format not in (0, 1):
+            raise ValueError("musig_nonce_agg: nonce_format and out_format must be 0 or 1")
+        if pubnonces is None:
+            raise ValueError("musig_nonce_agg: missing array")
+        pubnonces = _u8(pubnonces)
+        nonce_off = self._musig_off("musig_nonce_agg", nonce_off, 132 if nonce_format else 66, pubnonces)
+        n = nonce_off.size - 1
+        res = np.zeros(n, np.int32); out = np.zeros((132 if out_format else 66) * n, np.uint8)
+        self._check(self._lib.secp256k1_musig_nonce_agg_batch(self._h, _p(res), _p(out), out_format, _p(pubnonces), nonce_format, _p(nonce_off), n), "secp256k1_musig_nonce_agg_batch")
+        return res, out
+
+    def musig_nonce_agg_dev(self, results, aggnonces_out, pubnonces, nonce_off, nonce_format=0, out_format=0, stream=None):
+        """byte arrays in HBM (torch tensors); nonce_off is a HOST array; aggnonces_out feeds musig_nonce_process_dev on the same stream"""
+        nonce_off = self._musig_off("musig_nonce_agg_dev", nonce_off, 0, None)
+        self._check(self._lib.secp256k1_musig_nonce_agg_batch_dev(self._h, stream, _dp(results), _dp(aggnonces_out), out_format, _dp(pubnonces), nonce_format, _p(nonce_off),
+                                                                  nonce_off.size - 1), "secp256k1_musig_nonce_agg_batch_dev")
+
+    def musig_partial_sig_agg(self, sessions, partial_sigs, sig_off, sig_format=0):
+        """sessions n*133; partial_sigs 32 bytes serialised or 36-byte objects each, all sessions concatenated; session k owns
+        [sig_off[k], sig_off[k+1]).  Returns (verdicts, n*64 BIP-340 signatures, all zero where the verdict is 0)."""
+        if sig_format not in (0, 1):
+            raise ValueError("musig_partial_sig_agg: sig_format must be 0 or 1")
+        if sessions is None or partial_sigs is None:
+            raise ValueError("musig_partial_sig_agg: missing array")
+        sessions = _u8(sessions); partial_sigs = _u8(partial_sigs)
+        sig_off = self._musig_off("musig_partial_sig_agg", sig_off, 36 if sig_format else 32, partial_sigs)
+        n = sig_off.size - 1
+        _need("musig_partial_sig_agg sessions", sessions, 133 * n)
+        res = np.zeros(n, np.int32); out = np.zeros(64 * n, np.uint8)
+        self._check(self._lib.secp256k1_musig_partial_sig_agg_batch(self._h, _p(res), _p(out), _p(sessions), _p(partial_sigs), sig_format, _p(sig_off), n),
+                    "secp256k1_musig_partial_sig_agg_batch")
+        return res, out
+
+    def musig_partial_sig_agg_dev(self, results, sigs64_out, sessions, partial_sigs, sig_off, sig_format=0, stream=None):
+        """byte arrays in HBM (torch tensors); sig_off is a HOST array; sigs64_out are BIP-340 signatures"""
+        sig_off = self._musig_off("musig_partial_sig_agg_dev", sig_off, 0, None)
+        self._check(self._lib.secp256k1_musig_partial_sig_agg_batch_dev(self._h, stream, _dp(results), _dp(sigs64_out), _dp(sessions), _dp(partial_sigs), sig_format, _p(sig_off),
+                                                                        sig_off.size - 1), "secp256k1_musig_partial_sig_agg_batch_dev")
 
     # ---- secp256k1_xonly_pubkey_tweak_add_check / _tweak_add (modules/extrakeys/main_impl.h:118-154) and secp256k1_ec_pubkey_tweak_add (secp256k1.c:766-790), batched ----
     def xonly_tweak_add_check_batch(self, tweaked32, parities, internal_keys, tweaks32, key_format=0):

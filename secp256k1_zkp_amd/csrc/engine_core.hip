@@ -445,7 +445,7 @@ extern "C" s2k_engine* s2k_engine_create(int device) {
     for (int i = 0; i < 2; i++) { auto& m = e->msm_slot[i]; m.s = m.s2 = nullptr; m.fork = m.join = m.done = m.in = nullptr; m.ws = nullptr; m.ws_bytes = 0; m.seen_epoch = 0; }
     e->msm_seq = 0; e->cur_pipe = 0; e->ev_last_np = nullptr; e->np_epoch = 0; e->np_valid = 0;
     e->msm_pipeline = 0; e->halfagg_host_chain = 1; e->sync_split = 1; e->stage_log = 0;
-    e->msm_diag = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; e->msm_max_terms_opt = 0;
+    e->msm_diag = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; e->msm_max_terms_opt = 0; e->musig_sum_fanin = 0;
     for (int i = 0; i < 2; i++) { e->rp_mem[i] = nullptr; e->ev_rp_fork[i] = e->ev_rp_join[i] = e->ev_rp_pre[i] = e->ev_rp_done[i] = nullptr; e->rp_done_valid[i] = 0; }
     e->rp_debug = 0;
     for (int i = 0; i < 2; i++) { auto& S = e->stage[i]; S.in = S.out = S.dev = nullptr; S.in_bytes = S.out_bytes = S.dev_bytes = 0; S.ev_h2d = S.ev_out = nullptr; S.used = 0; S.ticket = 0; S.sync_owned = 0; }
@@ -816,6 +816,26 @@ extern "C" int secp256k1_musig_partial_sig_verify_amd(const void* ctx, const voi
                                                   (const unsigned char*)keyagg_cache, (const unsigned char*)session, 1, nullptr, 1)) return 0;
     return res;
 }
+// include/secp256k1_musig.h (src/modules/musig/keyagg_impl.h:156): the objects the pointers name are gathered and take the batch path
+// (the kernels live in engine_musig_agg.hip)
+extern "C" int secp256k1_musig_pubkey_agg_amd(const void* ctx, void* agg_pk, void* keyagg_cache, const void* const* pubkeys, size_t n_pubkeys) {
+    (void)ctx;
+    s2k_clear_status();
+    if (agg_pk) memset(agg_pk, 0, 64);
+    if (!pubkeys || n_pubkeys == 0) return s2k_fail_arg("secp256k1_musig_pubkey_agg_amd", "illegal argument (ARG_CHECK)");
+    for (size_t i = 0; i < n_pubkeys; i++) if (!pubkeys[i]) return s2k_fail_arg("secp256k1_musig_pubkey_agg_amd", "illegal argument (ARG_CHECK)");
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    std::vector<unsigned char> keys(64 * n_pubkeys);
+    for (size_t i = 0; i < n_pubkeys; i++) memcpy(&keys[64 * i], pubkeys[i], 64);
+    const uint64_t off[2] = {0, n_pubkeys};
+    unsigned char cache[197], xo[64];
+    int32_t res = 0;
+    if (!secp256k1_musig_pubkey_agg_batch(e, &res, cache, xo, keys.data(), 1, off, 1)) return 0;
+    if (res && keyagg_cache) memcpy(keyagg_cache, cache, 197);
+    if (res && agg_pk) memcpy(agg_pk, xo, 64);
+    return res;
+}
 // include/secp256k1_recovery.h:112 -- signature points at the 65-byte secp256k1_ecdsa_recoverable_signature object: the little-endian
 // limbs of r and s, then the recovery id (src/modules/recovery/main_impl.h:13-36); pubkey receives a secp256k1_pubkey object
 extern "C" int secp256k1_ecdsa_recover_amd(const void* ctx, void* pubkey, const void* signature, const unsigned char* msghash32) {
@@ -989,6 +1009,9 @@ extern "C" int s2k_engine_set_option(s2k_engine* e, int option, long value) {
     case S2K_OPT_MSM_MAX_TERMS:
         if (value != 0 && (value < 64 || (size_t)value > ((size_t(1) << 32) - 1) / 18 - 1)) return s2k_fail_arg("s2k_engine_set_option", "S2K_OPT_MSM_MAX_TERMS: 0 or 64 .. 238609293");
         e->msm_max_terms_opt = (size_t)value; return 1;
+    case S2K_OPT_MUSIG_SUM_FANIN:
+        if (value < 2 || value > 64) return s2k_fail_arg("s2k_engine_set_option", "S2K_OPT_MUSIG_SUM_FANIN: 2 .. 64");
+        e->musig_sum_fanin = (int)value; return 1;
     case S2K_OPT_GEN_CACHE_SLOTS: {                             // (the cache belongs to the device: every engine on it sees the change)
         s2k_dev_pool* p = e->pool;
         std::lock_guard<std::recursive_mutex> pool_lock(p->mu);

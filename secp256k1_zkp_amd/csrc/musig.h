@@ -6,8 +6,8 @@
 //                    mu = 1 for the cache's second key and the "KeyAgg coefficient" hash of pks_hash | ser33(P) otherwise,
 //                    sigma = -1 iff the session's parity byte is non-zero
 //   process (secp256k1_musig_nonce_process, session_impl.h:544-638): aggregate nonce, message and cache in, the 133-byte session out
-// Nothing here touches a secret: nonce generation, signing, adapt and extract stay with the reference, as do key aggregation, the
-// cache tweaks, nonce aggregation and signature aggregation.
+// Nothing here touches a secret: nonce generation, signing, adapt and extract stay with the reference.  Key aggregation, the cache
+// tweaks, nonce aggregation and signature aggregation are musig_agg.h.
 // The verifier takes the multi-exponentiation the reference's TODO (:741) asks for: T = (-s)*G + sigma*R1 through the fixed-base table
 // (tweak_gmul_fixed, no doubling), J = e'*P + (sigma*b)*R2 through the joint form ecmult_lane2 (128 doublings), or two ecmult_lane calls
 // for a wavefront it declines, and the verdict J == -T from one gej_add_var: no inversion.  Flag-and-select style as adaptor.h: an `ok`
