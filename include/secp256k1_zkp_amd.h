@@ -450,6 +450,68 @@ S2K_API int secp256k1_pedersen_commit_batch_dev(s2k_engine* e, void* stream, int
 S2K_API int secp256k1_schnorrsig_aggverify_amd(s2k_engine* e, int32_t* result, const unsigned char* pubkeys, int pk_format,
                                                const unsigned char* msgs32, size_t n, const unsigned char* aggsig, size_t aggsig_len);
 
+/* ---- half-aggregated Schnorr signatures: many aggregates per call, verification and aggregation ---------------------------
+ * One aggregate per call is a chain of latency-bound launches behind a serial hash chain; a caller with one small aggregate per
+ * transaction or per block has thousands of them.  These calls take K aggregates at once: one hash chain per GPU lane, the per-signature
+ * work one lane per signature over the whole batch, and the K sums in one launch chain (as s2k_ecmult_multi_many).  With both sides a
+ * node goes from signatures to aggregates to verdicts without leaving HBM.  All public data; nothing here is constant time.
+ * Conventions as in the MuSig2 aggregation section: results[] per aggregate; 0 and zeroed outputs for a refused aggregate, neighbours
+ * never affected; S2K_STATUS_ILLEGAL_ARGUMENT only for NULL where the reference has ARG_CHECK, a pk_format out of range, offsets that
+ * do not start at 0 or that decrease, n_before[k] above the aggregate's item count, and a batch above what one call indexes (2^40
+ * signatures, 2^46 aggregate bytes or 2^31 aggregates: "batch too large").  In the _dev forms every byte array is in HBM,
+ * results and outputs are zeroed on the stream first, and item_off, aggsig_off and n_before are HOST arrays (n_aggs + 1, n_aggs + 1
+ * and n_aggs entries), read before the call returns.  n_aggs == 0 returns 1.
+ * item_off counts signatures: aggregate k owns keys and messages [item_off[k], item_off[k+1]) of the back-to-back arrays (n_k of them).
+ * pk_format as above: 0 = 32-byte serialised x-only keys, 1 = 64-byte secp256k1_xonly_pubkey objects.
+ *
+ * results[k] = secp256k1_schnorrsig_aggverify(ctx, keys_k, msgs_k, n_k, aggsigs + aggsig_off[k], aggsig_off[k+1] - aggsig_off[k])
+ *                                       (src/modules/schnorrsig_halfagg/main_impl.h:108-198)
+ * aggsig_off holds BYTE offsets into aggsigs (like proof_off).  An aggregate whose length is not 32 (n_k + 1) gets verdict 0 and
+ * costs no key work (:122-125).  n_k == 0 is legal: the verdict is 1 exactly when s == 0.  An aggregate of more than 4 096
+ * signatures goes through the single-aggregate path (secp256k1_schnorrsig_aggverify_dev) behind the others, inside the same call.
+ *
+ * results[k] = secp256k1_schnorrsig_aggregate(ctx, out_k, &len, keys_k, msgs_k, sigs_k, n_k)              (:104-106, :19-102)
+ * sigs64: the n_k BIP-340 signatures of every aggregate, back to back (64 bytes each, item order).  Aggregate k is written at byte
+ * 32 (item_off[k] + k) of aggsigs_out and is 32 (n_k + 1) bytes long, so the output feeds the verifier with
+ * aggsig_off[k] = 32 (item_off[k] + k); aggsigs_out needs 32 (item_off[n_aggs] + n_aggs) bytes.  As in the reference s_i is reduced,
+ * not refused, and r_i is not checked.  results[k] == 0: a format-0 key that secp256k1_xonly_pubkey_parse refuses, or an all-zero
+ * key object (where the reference's xonly_pubkey_serialize fails).  DIFFERENCE FROM THE REFERENCE: the aggregate's 32 (n_k + 1)
+ * output bytes are then zero; the reference leaves the buffer untouched.
+ *
+ * results[k] = secp256k1_schnorrsig_inc_aggregate(ctx, out_k (holding aggregate k of aggsigs_in), &len, keys_k, msgs_k, new sigs of k,
+ *                                                 n_before[k], n_k - n_before[k])                          (:19-102)
+ * aggsigs_in: aggregate k is 32 (n_before[k] + 1) bytes (r_0 .. r_{n_before-1} | s_old), the aggregates packed back to back.
+ * new_sigs64: the n_k - n_before[k] new signatures of every aggregate, back to back.  The output layout is the aggregation call's
+ * (the old r_i are copied over).  As in the reference s_old is read without an overflow check, and only when n_before[k] > 0.
+ * secp256k1_schnorrsig_aggregate_batch is this call with every count 0 (and no aggsigs_in).
+ *
+ * Sizes.  The hash chain of ONE aggregate is walked by one GPU lane, about 3 us per 64-byte block and 1.5 blocks per signature, in the
+ * verifier up to 4 096 signatures per aggregate and in the aggregation calls whatever n_k is: these calls are for MANY aggregates of up
+ * to a few thousand signatures.  An aggregate of 2^20 signatures keeps a single kernel busy for about 5 s and the host plan takes 8
+ * bytes per signature of the longest aggregate; aggregate such a set in pieces (the incremental call continues an aggregate) or with
+ * the reference.
+ * Timing.  s2k_engine_last_ms(0) spans the call's launches, except that after a verification batch holding an over-limit aggregate it
+ * spans only the last single-aggregate launch; s2k_engine_last_ms(1) is the chain kernel in the aggregation calls and the bucket sums
+ * of the many-sums chain in the verification call (take the chain's time from an aggregation call over the same bytes).
+ *
+ * Out of scope: group forms of these calls, the hook into the reference's own functions (integration/), and bench.py. */
+S2K_API int secp256k1_schnorrsig_aggverify_batch(s2k_engine* e, int32_t* results, const unsigned char* pubkeys, int pk_format, const unsigned char* msgs32,
+                                                 const uint64_t* item_off, const unsigned char* aggsigs, const uint64_t* aggsig_off, size_t n_aggs);
+S2K_API int secp256k1_schnorrsig_aggverify_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* pubkeys, int pk_format,
+                                                     const unsigned char* msgs32, const uint64_t* item_off, const unsigned char* aggsigs,
+                                                     const uint64_t* aggsig_off, size_t n_aggs);
+S2K_API int secp256k1_schnorrsig_aggregate_batch(s2k_engine* e, int32_t* results, unsigned char* aggsigs_out, const unsigned char* pubkeys, int pk_format,
+                                                 const unsigned char* msgs32, const unsigned char* sigs64, const uint64_t* item_off, size_t n_aggs);
+S2K_API int secp256k1_schnorrsig_aggregate_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* aggsigs_out, const unsigned char* pubkeys,
+                                                     int pk_format, const unsigned char* msgs32, const unsigned char* sigs64, const uint64_t* item_off,
+                                                     size_t n_aggs);
+S2K_API int secp256k1_schnorrsig_inc_aggregate_batch(s2k_engine* e, int32_t* results, unsigned char* aggsigs_out, const unsigned char* aggsigs_in,
+                                                     const uint64_t* n_before, const unsigned char* pubkeys, int pk_format, const unsigned char* msgs32,
+                                                     const unsigned char* new_sigs64, const uint64_t* item_off, size_t n_aggs);
+S2K_API int secp256k1_schnorrsig_inc_aggregate_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* aggsigs_out, const unsigned char* aggsigs_in,
+                                                         const uint64_t* n_before, const unsigned char* pubkeys, int pk_format, const unsigned char* msgs32,
+                                                         const unsigned char* new_sigs64, const uint64_t* item_off, size_t n_aggs);
+
 /* ---- Borromean rangeproof batch verification ---------------------------------------------------------------------
  * results[i], min_value[i], max_value[i] = secp256k1_rangeproof_verify(ctx, &min, &max, commit_i, proof_i, plen_i,
  *                                          extra_commit_i, extra_commit_len_i, gen_i)

@@ -77,6 +77,12 @@ SIGNATURES = {
     "secp256k1_whitelist_verify_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),
     "secp256k1_whitelist_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz]),
     "secp256k1_schnorrsig_aggverify_amd": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _sz, _vp, _sz]),
+    "secp256k1_schnorrsig_aggverify_batch": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_schnorrsig_aggverify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_schnorrsig_aggregate_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _vp, _sz]),
+    "secp256k1_schnorrsig_aggregate_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _vp, _sz]),
+    "secp256k1_schnorrsig_inc_aggregate_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _vp, _sz]),
+    "secp256k1_schnorrsig_inc_aggregate_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _vp, _sz]),
     "secp256k1_pedersen_verify_tally_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "secp256k1_rangeproof_verify_batch": (_c.c_int, [_vp] + [_vp] * 9 + [_sz]),
     "secp256k1_rangeproof_verify_batch_ptrs": (_c.c_int, [_vp] + [_vp] * 9 + [_sz]),

@@ -666,6 +666,75 @@ class Engine:
                                                                  _p(aggsig), aggsig.size), "secp256k1_schnorrsig_aggverify_amd")
         return int(res[0])
 
+    # ---- many half-aggregates per call (include/secp256k1_zkp_amd.h: verification as K sums in one launch chain, and aggregation) ----
+    @staticmethod
+    def _halfagg_items(what, keys, msgs, pk_format):
+        """lists of per-aggregate byte strings -> (keys array, msgs array, item_off, counts)"""
+        if pk_format not in (0, 1):
+            raise ValueError(f"{what}: pk_format must be 0 (32-byte x-only keys) or 1 (64-byte objects)")
+        if keys is None or msgs is None or len(keys) != len(msgs):
+            raise ValueError(f"{what}: one key string and one message string per aggregate")
+        pkb = 64 if pk_format else 32
+        counts = []
+        for k, (pk, m) in enumerate(zip(keys, msgs)):
+            pk, m = bytes(pk), bytes(m)
+            if len(m) % 32 or len(pk) != pkb * (len(m) // 32):
+                raise ValueError(f"{what}: aggregate {k} needs 32 message bytes and {pkb} key bytes per signature")
+            counts.append(len(m) // 32)
+        off = np.zeros(len(counts) + 1, np.uint64); off[1:] = np.cumsum(np.array(counts, np.uint64), dtype=np.uint64)
+        return _u8(b"".join(bytes(x) for x in keys)), _u8(b"".join(bytes(x) for x in msgs)), off, counts
+
+    def schnorrsig_aggverify_batch(self, pubkeys, msgs32, aggsigs, pk_format=0):
+        """pubkeys, msgs32, aggsigs: lists with one byte string per aggregate (n_k keys, n_k messages, r_0..r_{n_k-1}|s).  Returns int32
+        verdicts, the reference's secp256k1_schnorrsig_aggverify per aggregate (a wrong-length aggregate gets 0)."""
+        keys, msgs, off, counts = self._halfagg_items("schnorrsig_aggverify_batch", pubkeys, msgs32, pk_format)
+        if aggsigs is None or len(aggsigs) != len(counts):
+            raise ValueError("schnorrsig_aggverify_batch: one aggregate per key string")
+        agg, agg_off = self.pack([bytes(a) for a in aggsigs])
+        n = len(counts); res = np.zeros(max(n, 1), np.int32)
+        self._check(self._lib.secp256k1_schnorrsig_aggverify_batch(self._h, _p(res), _p(keys) if keys.size else None, pk_format, _p(msgs) if msgs.size else None, _p(off),
+                                                                   _p(agg) if agg.size else _p(np.zeros(1, np.uint8)), _p(agg_off), n), "secp256k1_schnorrsig_aggverify_batch")
+        return res[:n]
+
+    def schnorrsig_inc_aggregate_batch(self, aggsigs_in, pubkeys, msgs32, new_sigs64, pk_format=0):
+        """aggsigs_in: per aggregate the 32 (n_before + 1) bytes it already has (None: the plain aggregation, n_before = 0 everywhere);
+        pubkeys, msgs32: ALL n_k keys and messages per aggregate; new_sigs64: the n_k - n_before new signatures per aggregate.
+        Returns (verdicts, list of aggregates: 32 (n_k + 1) bytes each, all zero where the verdict is 0)."""
+        what = "schnorrsig_inc_aggregate_batch"
+        keys, msgs, off, counts = self._halfagg_items(what, pubkeys, msgs32, pk_format)
+        n = len(counts)
+        if new_sigs64 is None or len(new_sigs64) != n or (aggsigs_in is not None and len(aggsigs_in) != n):
+            raise ValueError(f"{what}: one string per aggregate in every list")
+        before = []
+        for k in range(n):
+            old = 0
+            if aggsigs_in is not None:
+                ln = len(bytes(aggsigs_in[k]))
+                if ln % 32 or ln == 0:
+                    raise ValueError(f"{what}: aggregate {k} of aggsigs_in must be 32 (n_before + 1) bytes")
+                old = ln // 32 - 1
+            ns = len(bytes(new_sigs64[k]))
+            if ns % 64 or old + ns // 64 != counts[k]:
+                raise ValueError(f"{what}: aggregate {k} has {counts[k]} keys but {old} + {ns // 64} signatures")
+            before.append(old)
+        sigs = _u8(b"".join(bytes(x) for x in new_sigs64))
+        res = np.zeros(max(n, 1), np.int32); out = np.zeros(32 * (int(off[-1]) + n) + 1, np.uint8)
+        if aggsigs_in is None:
+            ok = self._lib.secp256k1_schnorrsig_aggregate_batch(self._h, _p(res), _p(out), _p(keys) if keys.size else None, pk_format, _p(msgs) if msgs.size else None,
+                                                                _p(sigs) if sigs.size else None, _p(off), n)
+            self._check(ok, "secp256k1_schnorrsig_aggregate_batch")
+        else:
+            old = _u8(b"".join(bytes(x) for x in aggsigs_in)); nb = np.array(before + [0], np.uint64)
+            ok = self._lib.secp256k1_schnorrsig_inc_aggregate_batch(self._h, _p(res), _p(out), _p(old) if old.size else _p(np.zeros(1, np.uint8)), _p(nb),
+                                                                    _p(keys) if keys.size else None, pk_format, _p(msgs) if msgs.size else None,
+                                                                    _p(sigs) if sigs.size else None, _p(off), n)
+            self._check(ok, "secp256k1_schnorrsig_inc_aggregate_batch")
+        return res[:n], [out[32 * (int(off[k]) + k):32 * (int(off[k + 1]) + k + 1)].tobytes() for k in range(n)]
+
+    def schnorrsig_aggregate_batch(self, pubkeys, msgs32, sigs64, pk_format=0):
+        """lists with one byte string per aggregate (n_k keys, messages, 64-byte signatures) -> (verdicts, list of 32 (n_k + 1)-byte aggregates)"""
+        return self.schnorrsig_inc_aggregate_batch(None, pubkeys, msgs32, sigs64, pk_format)
+
     # ---- secp256k1_pedersen_verify_tally (modules/generator/main_impl.h:371-396), batched -------------------------
     def pedersen_verify_tally_batch(self, tallies):
         """tallies: list of (positive, negative), each a (k,33) uint8 array (or list of 33-byte strings) of serialised commitments.

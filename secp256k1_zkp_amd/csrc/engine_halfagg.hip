@@ -67,14 +67,13 @@ __global__ void k_ha_final(int32_t* result, const u32* flags, const u32* res28) 
     if (threadIdx.x || blockIdx.x) return;
     *result = (flags[0] == 0u) && (res28[27] != 0u);
 }
-static size_t ha_ws_bytes(const s2k_engine* e, size_t n) {
+size_t ha_ws_bytes(const s2k_engine* e, size_t n) {
     const size_t nblocks = (3 * n) >> 1, nt = 2 * n + 1;
     return ws_need({128 * n + 64, 32 * n + 64, nblocks * 256 + 64, nblocks * 32 + 64, 64 * n + 64, 64, 64, 16}) + msm_ws_bytes(e, nt + 1, engine_msm_plan(e, nt));
 }
 // The randomizer hash's chain on the host (host_sha256.h): state after every full 64-byte block of r_0|x(P_0)|m_0|r_1|..., into pinned
 // memory.  pk_format 0: the serialised key IS x(P_i) (a key that does not parse makes the verdict 0 whatever is hashed); 1: the object's
 // first 32 bytes are x, least significant byte first.
-struct ha_host_src { const unsigned char* aggsig; const unsigned char* pks; int pk_format; const unsigned char* msgs32; };
 static void ha_host_chain(u32* states, const ha_host_src& h, size_t nblocks) {
     uint32_t st[8]; ha_tag_midstate(st);
     const size_t pkb = h.pk_format ? 64 : 32;
@@ -95,8 +94,8 @@ static void ha_host_chain(u32* states, const ha_host_src& h, size_t nblocks) {
 // device pointers in, verdict to d_res[0]; aggsig_len already checked to be 32 (n + 1).  host: the same inputs in host memory -- the
 // hash chain is then walked on the host underneath the point-lifting kernel and its states uploaded (the device chain is 2.4 us per
 // block on one wavefront: 118 ms for 2^15 signatures against ~2.6 ms here); nullptr: the device chain.
-static int ha_launch(s2k_engine* e, hipStream_t st, ws_carver& c, int32_t* d_res, const unsigned char* d_pk, int pk_format, const unsigned char* d_msg, size_t n,
-                     const unsigned char* d_agg, const ha_host_src* host = nullptr, const u32* d_states_in = nullptr) {
+int ha_launch(s2k_engine* e, hipStream_t st, ws_carver& c, int32_t* d_res, const unsigned char* d_pk, int pk_format, const unsigned char* d_msg, size_t n,
+              const unsigned char* d_agg, const ha_host_src* host, const u32* d_states_in) {
     const size_t nblocks = (3 * n) >> 1;
     unsigned char* d_pts = c.take<unsigned char>(128 * n + 64);
     unsigned char* d_pkx = c.take<unsigned char>(32 * n + 64); u32* d_wk = c.take<u32>(nblocks * 64 + 16); u32* d_states = c.take<u32>(nblocks * 8 + 16);

@@ -1,7 +1,7 @@
 // engine_internal.h -- what the translation units of the gfx950 batch-verification engine share (see include/secp256k1_zkp_amd.h):
 // the engine object, the per-device table pool, error plumbing, workspace carving and the host functions one kernel family offers the others.
 //
-// The library is thirteen translation units, one per kernel family, compiled separately (hipcc --offload-arch=gfx950 -O3 -fPIC -c) and linked
+// The library is fourteen translation units, one per kernel family, compiled separately (hipcc --offload-arch=gfx950 -O3 -fPIC -c) and linked
 // into one shared object (see __graft_entry__.build):
 //   engine_core.hip        table construction, the per-device pool and generator-table cache, engine lifecycle / options / groups,
 //                          s2k_ecmult_batch, BIP-340, the single-item `_amd` forms and the `_group` forms of every family
@@ -10,6 +10,7 @@
 //   engine_bppp.hip        Bulletproofs++ norm argument verification and bppp_commit
 //   engine_msm_many.hip    K independent multi-scalar multiplications in one launch chain
 //   engine_halfagg.hip     half-aggregated Schnorr verification
+//   engine_halfagg_batch.hip  many half-aggregates per call: batch verification and (incremental) aggregation (halfagg_batch.h)
 //   engine_ecdsa.hip       ECDSA verification and public-key recovery (ecdsa.h)
 //   engine_whitelist.hip   whitelist-signature verification (whitelist.h)
 //   engine_tweak.hip       Taproot tweak checks and public-key tweak-add (tweak.h)
@@ -252,3 +253,14 @@ int msm_launch(s2k_engine* e, hipStream_t st, ws_carver& c, u32** result28, cons
 // segmented tree sum of Jacobian records, ping-ponging between two scratch buffers; returns where the nseg results are
 const u32* launch_gej_reduce(hipStream_t st, const u32* in, u32* bufA, u32* bufB, u32 nseg, u32 seg_len, const u32* gate = nullptr);
 void launch_set_word(hipStream_t st, u32* p, u32 v);
+// ---- K sums in one launch chain (engine_msm_many.hip), for the families that feed it from their own kernels ----------------------------------
+#define MM_MAX_TERMS 8192u        /* (engine_msm_many.hip defines the same: sums above it make mm_impl run the WHOLE call one sum after the other) */
+size_t mm_ws_bytes(const s2k_engine* e, const uint64_t* off_host, size_t K, u32 has_g);
+int mm_impl(s2k_engine* e, hipStream_t st, size_t front, unsigned char* d_rxy, int32_t* d_rinf, const unsigned char* d_g, const unsigned char* d_sc,
+            const unsigned char* d_pt, const unsigned char* d_inf, const uint64_t* off_host, size_t K);
+int mm_check_offsets(const char* who, const uint64_t* off, size_t K);
+// ---- one half-aggregate (engine_halfagg.hip) ---------------------------------------------------------------------------------------------------
+struct ha_host_src { const unsigned char* aggsig; const unsigned char* pks; int pk_format; const unsigned char* msgs32; };
+size_t ha_ws_bytes(const s2k_engine* e, size_t n);
+int ha_launch(s2k_engine* e, hipStream_t st, ws_carver& c, int32_t* d_res, const unsigned char* d_pk, int pk_format, const unsigned char* d_msg, size_t n,
+              const unsigned char* d_agg, const ha_host_src* host = nullptr, const u32* d_states_in = nullptr);

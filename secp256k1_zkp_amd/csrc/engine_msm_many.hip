@@ -189,7 +189,7 @@ static u32 mm_pick_c(size_t n) {
 }
 
 // workspace of one call beyond `front` bytes of staged inputs (sized once, up front: growing the workspace moves it)
-static size_t mm_ws_bytes(const s2k_engine* e, const uint64_t* off_host, size_t K, u32 has_g) {
+size_t mm_ws_bytes(const s2k_engine* e, const uint64_t* off_host, size_t K, u32 has_g) {
     const size_t N = (size_t)off_host[K];
     size_t nmax = 0;
     for (size_t s = 0; s < K; s++) nmax = std::max(nmax, (size_t)(off_host[s + 1] - off_host[s]));
@@ -203,8 +203,8 @@ static size_t mm_ws_bytes(const s2k_engine* e, const uint64_t* off_host, size_t 
     return ws_need({(K + 1) * 8, nt * MSM_TERM_WORDS * 4, nt * MSM_HALF_WORDS * 4, 2 * (size_t)W * nt * 4 + 64, nsw * (nb + 1) * 4, nsw * nb * 28 * 4, (nsw + 64) * 28 * 4, (nsw + 64) * 28 * 4});
 }
 // offsets (host, K + 1 entries) are read before the call returns; everything else is stream-ordered.  dev = 1: device pointers.
-static int mm_impl(s2k_engine* e, hipStream_t st, size_t front, unsigned char* d_rxy, int32_t* d_rinf, const unsigned char* d_g, const unsigned char* d_sc,
-                   const unsigned char* d_pt, const unsigned char* d_inf, const uint64_t* off_host, size_t K) {
+int mm_impl(s2k_engine* e, hipStream_t st, size_t front, unsigned char* d_rxy, int32_t* d_rinf, const unsigned char* d_g, const unsigned char* d_sc,
+            const unsigned char* d_pt, const unsigned char* d_inf, const uint64_t* off_host, size_t K) {
     const size_t N = (size_t)off_host[K];
     size_t nmax = 0;
     for (size_t s = 0; s < K; s++) nmax = std::max(nmax, (size_t)(off_host[s + 1] - off_host[s]));
@@ -257,7 +257,7 @@ static int mm_impl(s2k_engine* e, hipStream_t st, size_t front, unsigned char* d
     HIPCHK(hipEventSynchronize(e->ev_fork));
     return 1;
 }
-static int mm_check_offsets(const char* who, const uint64_t* off, size_t K) {
+int mm_check_offsets(const char* who, const uint64_t* off, size_t K) {
     if (!off) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     if (off[0] != 0) return s2k_fail_arg(who, "offsets must start at 0");
     for (size_t s = 0; s < K; s++) if (off[s + 1] < off[s]) return s2k_fail_arg(who, "offsets must not decrease");
