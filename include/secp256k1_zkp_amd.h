@@ -80,6 +80,9 @@ S2K_API void s2k_clear_status(void);
  *   slots: 0.44 / 1.6 / 5.9 / 21.5 GB each, one more addition per fixed-base multiplication for every step down).  Changing it gives the device's
  *   tables back (after a device-wide wait: an administrative call) and the next call that needs one builds it at the new width; a width that
  *   does not fit still falls back to the next narrower one.  Results do not depend on it.
+ * S2K_OPT_S2C_FUSED (default 0): secp256k1_anti_exfil_host_verify_batch runs the commitment check and the ECDSA verification in one kernel
+ *   instead of the default chain of two (the commitment kernel's verdicts into a byte array, then an ECDSA kernel that ANDs them in).
+ *   Results do not depend on it; the chain is the default because it measured faster (tools/s2c_bare.py).
  * Environment: only start-up defaults are read from it, once, when an engine (or the device's table pool) is created: S2K_DEVICE,
  * S2K_GEN_CACHE, S2K_GEN_CACHE_MIN, S2K_STAGE_THREADS, S2K_GTAB_BITS.  Nothing on a call path reads the environment. */
 #define S2K_OPT_RP_INPUTS_READY 1
@@ -94,6 +97,7 @@ S2K_API void s2k_clear_status(void);
 #define S2K_OPT_MSM_MAX_TERMS 10
 #define S2K_OPT_GTAB_BITS 11
 #define S2K_OPT_MUSIG_SUM_FANIN 12
+#define S2K_OPT_S2C_FUSED 13
 S2K_API int s2k_engine_set_option(s2k_engine* e, int option, long value);
 /* Rangeproof generator tables.  The four public keys of a Borromean ring differ by multiples of the proof's generator
  * (secp256k1_rangeproof_pub_expand, src/modules/rangeproof/rangeproof_impl.h:19-51), so when the engine holds a fixed-base table of that
@@ -238,6 +242,34 @@ S2K_API int secp256k1_ecdsa_adaptor_verify_batch(s2k_engine* e, int32_t* results
                                                  const unsigned char* msgs32, const unsigned char* enckeys, int pk_format, size_t n);
 S2K_API int secp256k1_ecdsa_adaptor_verify_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* adaptor_sigs162,
                                                      const unsigned char* pubkeys, const unsigned char* msgs32, const unsigned char* enckeys, int pk_format, size_t n);
+
+/* ---- ECDSA sign-to-contract checks and anti-exfil host verification ----------------------------------------------------
+ * verify_commit:  results[i] = signature_i and opening_i parse &&
+ *              secp256k1_ecdsa_s2c_verify_commit(ctx, sig_i, data32 + 32 i, opening_i)
+ *                                       (include/secp256k1_ecdsa_s2c.h, src/modules/ecdsa_s2c/main_impl.h:88-128;
+ *                                        the commitment: secp256k1_ec_commit, src/eccommit_impl.h:48-72)
+ * host_verify:    results[i] = signature_i, opening_i and public key_i parse &&
+ *              secp256k1_anti_exfil_host_verify(ctx, sig_i, msghash32 + 32 i, pubkey_i, host_data32 + 32 i, opening_i)
+ *                                       (src/modules/ecdsa_s2c/main_impl.h:185-188: verify_commit, then secp256k1_ecdsa_verify)
+ * host_commit:    commitments_out32 + 32 i = what secp256k1_ecdsa_anti_exfil_host_commit(ctx, ., rand32 + 32 i) writes (:131-144)
+ * sigs, sig_off, sig_format, pubkeys and pk_format mean what they mean in secp256k1_ecdsa_verify_batch (with DER, sig_off is a host
+ * array in the host and group forms and a device array in the _dev forms).  The commitment check reads r alone: a high or zero s passes
+ * it and fails host_verify.  openings: opening_format 0: n*33 compressed, as secp256k1_ecdsa_s2c_opening_parse reads them;
+ * 1: n*64 `secp256k1_ecdsa_s2c_opening` objects, which have the layout of `secp256k1_pubkey` (an all-zero x gives 0).
+ * Only the host's and the auditor's side is served: it reads public data.  secp256k1_ecdsa_s2c_sign, secp256k1_ecdsa_anti_exfil_signer_commit
+ * and secp256k1_anti_exfil_sign handle secrets and need the reference's constant-time code. */
+S2K_API int secp256k1_ecdsa_s2c_verify_commit_batch(s2k_engine* e, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
+                                                    const unsigned char* data32, const unsigned char* openings, int opening_format, size_t n);
+S2K_API int secp256k1_ecdsa_s2c_verify_commit_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off,
+                                                        int sig_format, const unsigned char* data32, const unsigned char* openings, int opening_format, size_t n);
+S2K_API int secp256k1_anti_exfil_host_verify_batch(s2k_engine* e, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
+                                                   const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format, const unsigned char* host_data32,
+                                                   const unsigned char* openings, int opening_format, size_t n);
+S2K_API int secp256k1_anti_exfil_host_verify_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off,
+                                                       int sig_format, const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format,
+                                                       const unsigned char* host_data32, const unsigned char* openings, int opening_format, size_t n);
+S2K_API int secp256k1_ecdsa_anti_exfil_host_commit_batch(s2k_engine* e, unsigned char* commitments_out32, const unsigned char* rand32, size_t n);
+S2K_API int secp256k1_ecdsa_anti_exfil_host_commit_batch_dev(s2k_engine* e, void* stream, unsigned char* commitments_out32, const unsigned char* rand32, size_t n);
 
 /* ---- MuSig2: batch partial-signature verification and nonce processing (the coordinator's half) ------------------------
  * results[i] = inputs parse &&
@@ -596,6 +628,13 @@ S2K_API int secp256k1_ecdsa_recover_amd(const void* ctx, void* pubkey, const voi
  * pubkey, enckey: 64-byte secp256k1_pubkey objects. */
 S2K_API int secp256k1_ecdsa_adaptor_verify_amd(const void* ctx, const unsigned char* adaptor_sig162, const void* pubkey, const unsigned char* msg32,
                                                const void* enckey);
+/*   secp256k1_ecdsa_s2c_verify_commit(ctx, sig, data32, opening)                       include/secp256k1_ecdsa_s2c.h,
+ *                                                                                      src/modules/ecdsa_s2c/main_impl.h:88
+ *   secp256k1_anti_exfil_host_verify(ctx, sig, msg32, pubkey, host_data32, opening)    src/modules/ecdsa_s2c/main_impl.h:185
+ * sig: the 64-byte secp256k1_ecdsa_signature object; pubkey, opening: 64-byte secp256k1_pubkey / secp256k1_ecdsa_s2c_opening objects. */
+S2K_API int secp256k1_ecdsa_s2c_verify_commit_amd(const void* ctx, const void* sig, const unsigned char* data32, const void* opening);
+S2K_API int secp256k1_anti_exfil_host_verify_amd(const void* ctx, const void* sig, const unsigned char* msg32, const void* pubkey, const unsigned char* host_data32,
+                                                 const void* opening);
 /*   secp256k1_musig_partial_sig_verify(ctx, partial_sig, pubnonce, pubkey, keyagg_cache, session)      include/secp256k1_musig.h,
  *                                                                                      src/modules/musig/session_impl.h:716
  * all five point at the reference's objects (36, 132, 64, 197 and 133 bytes). */
@@ -741,6 +780,11 @@ S2K_API int secp256k1_ecdsa_verify_batch_group(s2k_group* g, int32_t* results, c
                                                const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format, size_t n);
 S2K_API int secp256k1_ecdsa_adaptor_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* adaptor_sigs162, const unsigned char* pubkeys,
                                                        const unsigned char* msgs32, const unsigned char* enckeys, int pk_format, size_t n);
+S2K_API int secp256k1_ecdsa_s2c_verify_commit_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
+                                                          const unsigned char* data32, const unsigned char* openings, int opening_format, size_t n);
+S2K_API int secp256k1_anti_exfil_host_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
+                                                         const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format, const unsigned char* host_data32,
+                                                         const unsigned char* openings, int opening_format, size_t n);
 /* (every engine gets its share of the items and the whole cache / session arrays) */
 S2K_API int secp256k1_musig_partial_sig_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* partial_sigs, int sig_format,
                                                            const unsigned char* pubnonces, int nonce_format, const unsigned char* pubkeys, int pk_format,

@@ -96,6 +96,16 @@ SIGNATURES = {
     "secp256k1_ecdsa_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "secp256k1_ecdsa_recover_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "secp256k1_ecdsa_adaptor_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "secp256k1_ecdsa_s2c_verify_commit_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_ecdsa_s2c_verify_commit_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_anti_exfil_host_verify_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_anti_exfil_host_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_ecdsa_anti_exfil_host_commit_batch": (_c.c_int, [_vp, _vp, _vp, _sz]),
+    "secp256k1_ecdsa_anti_exfil_host_commit_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _sz]),
+    "secp256k1_ecdsa_s2c_verify_commit_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_anti_exfil_host_verify_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_ecdsa_s2c_verify_commit_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
+    "secp256k1_anti_exfil_host_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "secp256k1_musig_partial_sig_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "secp256k1_musig_pubkey_agg_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _sz]),
     "secp256k1_whitelist_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _vp]),

@@ -105,6 +105,22 @@ def _musig_verify_args(what, partial_sigs, pubnonces, pubkeys, keyagg_caches, se
     return partial_sigs, pubnonces, pubkeys, keyagg_caches, sessions, session_of, ns, n
 
 
+def _s2c_args(what, sigs, data32, openings, sig_format, opening_format, msghashes=None, pubkeys=None, pk_format=0, full=False):
+    """shape checks shared by the sign-to-contract methods of Engine and Group: signatures (and, when full, message hashes and keys) through
+    _ecdsa_args; returns (sigs, sig_off or None, msghashes, pubkeys, data32, openings, n)"""
+    if opening_format not in (0, 1):
+        raise ValueError(f"{what}: opening_format must be 0 (n*33 compressed) or 1 (n*64 opening objects)")
+    if data32 is None or openings is None or (full and (msghashes is None or pubkeys is None)):
+        raise ValueError(f"{what}: missing array")
+    data32 = _u8(data32); openings = _u8(openings)
+    if full:
+        sigs, off, msghashes, pubkeys, n = _ecdsa_args(what, sigs, msghashes, pubkeys, sig_format, pk_format)
+    else:                                            # the commitment check reads neither: the data stands in where _ecdsa_args counts 32 bytes per item
+        sigs, off, _, _, n = _ecdsa_args(what, sigs, data32, openings, sig_format, opening_format)
+    _need(what + " data32", data32, 32 * n); _need(what + " openings", openings, (64 if opening_format else 33) * n)
+    return sigs, off, msghashes, pubkeys, data32, openings, n
+
+
 _TWEAK_KEY_BYTES = {0: 32, 1: 64, 2: 33}     # serialised x-only / secp256k1_xonly_pubkey or secp256k1_pubkey object / compressed
 
 
@@ -160,6 +176,7 @@ class Engine:
     OPT_MSM_MAX_TERMS = 10
     OPT_GTAB_BITS = 11
     OPT_MUSIG_SUM_FANIN = 12
+    OPT_S2C_FUSED = 13
 
     def cache_generator(self, gen64):
         """Build the fixed-base table of one rangeproof generator now (s2k_engine_cache_generator)."""
@@ -330,6 +347,59 @@ class Engine:
         n = adaptor_sigs.numel() // 162 if n is None else n
         self._check(self._lib.secp256k1_ecdsa_adaptor_verify_batch_dev(self._h, stream, _dp(results), _dp(adaptor_sigs), _dp(pubkeys), _dp(msgs32), _dp(enckeys),
                                                                        pk_format, n), "secp256k1_ecdsa_adaptor_verify_batch_dev")
+
+    # ---- secp256k1_ecdsa_s2c_verify_commit, secp256k1_anti_exfil_host_verify and secp256k1_ecdsa_anti_exfil_host_commit (modules/ecdsa_s2c/main_impl.h:88-188), batched ----
+    def ecdsa_s2c_verify_commit_batch(self, sigs, data32, openings, sig_format=0, opening_format=0):
+        """sigs and sig_format as ecdsa_verify_batch; data32 n*32; openings: opening_format 0: n*33 compressed, 1: n*64 secp256k1_ecdsa_s2c_opening objects"""
+        sigs, off, _, _, data32, openings, n = _s2c_args("ecdsa_s2c_verify_commit_batch", sigs, data32, openings, sig_format, opening_format)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_ecdsa_s2c_verify_commit_batch(self._h, _p(res), _p(sigs), _p(off), sig_format, _p(data32), _p(openings), opening_format, n),
+                    "secp256k1_ecdsa_s2c_verify_commit_batch")
+        return res
+
+    def ecdsa_s2c_verify_commit_batch_dev(self, results, sigs, data32, openings, sig_format=0, opening_format=0, sig_off=None, n=None, stream=None):
+        """every array in HBM (torch tensors; sig_off: int64 / uint64 offsets[n+1], DER only)"""
+        if sig_format == 2 and sig_off is None:
+            raise ValueError("ecdsa_s2c_verify_commit_batch_dev: DER signatures need sig_off")
+        if n is None:
+            n = sig_off.numel() - 1 if sig_format == 2 else sigs.numel() // 64
+        self._check(self._lib.secp256k1_ecdsa_s2c_verify_commit_batch_dev(self._h, stream, _dp(results), _dp(sigs), _dp(sig_off) if sig_format == 2 else None, sig_format,
+                                                                          _dp(data32), _dp(openings), opening_format, n), "secp256k1_ecdsa_s2c_verify_commit_batch_dev")
+
+    def anti_exfil_host_verify_batch(self, sigs, msghashes, pubkeys, host_data32, openings, sig_format=0, pk_format=0, opening_format=0):
+        """sigs, msghashes, pubkeys, sig_format and pk_format as ecdsa_verify_batch; host_data32 n*32; openings as ecdsa_s2c_verify_commit_batch"""
+        sigs, off, msghashes, pubkeys, host_data32, openings, n = _s2c_args("anti_exfil_host_verify_batch", sigs, host_data32, openings, sig_format, opening_format,
+                                                                            msghashes, pubkeys, pk_format, full=True)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_anti_exfil_host_verify_batch(self._h, _p(res), _p(sigs), _p(off), sig_format, _p(msghashes), _p(pubkeys), pk_format,
+                                                                     _p(host_data32), _p(openings), opening_format, n), "secp256k1_anti_exfil_host_verify_batch")
+        return res
+
+    def anti_exfil_host_verify_batch_dev(self, results, sigs, msghashes, pubkeys, host_data32, openings, sig_format=0, pk_format=0, opening_format=0, sig_off=None,
+                                         n=None, stream=None):
+        """every array in HBM (torch tensors; sig_off: int64 / uint64 offsets[n+1], DER only)"""
+        if sig_format == 2 and sig_off is None:
+            raise ValueError("anti_exfil_host_verify_batch_dev: DER signatures need sig_off")
+        if n is None:
+            n = sig_off.numel() - 1 if sig_format == 2 else sigs.numel() // 64
+        self._check(self._lib.secp256k1_anti_exfil_host_verify_batch_dev(self._h, stream, _dp(results), _dp(sigs), _dp(sig_off) if sig_format == 2 else None, sig_format,
+                                                                         _dp(msghashes), _dp(pubkeys), pk_format, _dp(host_data32), _dp(openings), opening_format, n),
+                    "secp256k1_anti_exfil_host_verify_batch_dev")
+
+    def anti_exfil_host_commit_batch(self, rand32):
+        """-> commitments[n, 32]: what secp256k1_ecdsa_anti_exfil_host_commit writes for each 32-byte input"""
+        if rand32 is None:
+            raise ValueError("anti_exfil_host_commit_batch: missing array")
+        rand32 = _u8(rand32); n = rand32.size // 32
+        _need("anti_exfil_host_commit_batch rand32", rand32, 32 * n)
+        out = np.zeros((n, 32), np.uint8)
+        self._check(self._lib.secp256k1_ecdsa_anti_exfil_host_commit_batch(self._h, _p(out), _p(rand32), n), "secp256k1_ecdsa_anti_exfil_host_commit_batch")
+        return out
+
+    def anti_exfil_host_commit_batch_dev(self, commitments_out32, rand32, n=None, stream=None):
+        n = rand32.numel() // 32 if n is None else n
+        self._check(self._lib.secp256k1_ecdsa_anti_exfil_host_commit_batch_dev(self._h, stream, _dp(commitments_out32), _dp(rand32), n),
+                    "secp256k1_ecdsa_anti_exfil_host_commit_batch_dev")
 
     # ---- secp256k1_musig_partial_sig_verify and secp256k1_musig_nonce_process (modules/musig/session_impl.h:716-777, :588-638), batched ----
     def musig_partial_sig_verify(self, partial_sigs, pubnonces, pubkeys, keyagg_caches, sessions, session_of=None, sig_format=0, nonce_format=0, pk_format=0):
@@ -949,6 +1019,21 @@ class Group:
         res = np.zeros(n, np.int32)
         self._check(self._lib.secp256k1_ecdsa_adaptor_verify_batch_group(self._h, _p(res), _p(adaptor_sigs), _p(pubkeys), _p(msgs32), _p(enckeys), pk_format, n),
                     "secp256k1_ecdsa_adaptor_verify_batch_group")
+        return res
+
+    def ecdsa_s2c_verify_commit_batch(self, sigs, data32, openings, sig_format=0, opening_format=0):
+        sigs, off, _, _, data32, openings, n = _s2c_args("ecdsa_s2c_verify_commit_batch_group", sigs, data32, openings, sig_format, opening_format)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_ecdsa_s2c_verify_commit_batch_group(self._h, _p(res), _p(sigs), _p(off), sig_format, _p(data32), _p(openings), opening_format, n),
+                    "secp256k1_ecdsa_s2c_verify_commit_batch_group")
+        return res
+
+    def anti_exfil_host_verify_batch(self, sigs, msghashes, pubkeys, host_data32, openings, sig_format=0, pk_format=0, opening_format=0):
+        sigs, off, msghashes, pubkeys, host_data32, openings, n = _s2c_args("anti_exfil_host_verify_batch_group", sigs, host_data32, openings, sig_format, opening_format,
+                                                                            msghashes, pubkeys, pk_format, full=True)
+        res = np.zeros(n, np.int32)
+        self._check(self._lib.secp256k1_anti_exfil_host_verify_batch_group(self._h, _p(res), _p(sigs), _p(off), sig_format, _p(msghashes), _p(pubkeys), pk_format,
+                                                                           _p(host_data32), _p(openings), opening_format, n), "secp256k1_anti_exfil_host_verify_batch_group")
         return res
 
     def xonly_tweak_add_check_batch(self, tweaked32, parities, internal_keys, tweaks32, key_format=0):

@@ -445,7 +445,7 @@ extern "C" s2k_engine* s2k_engine_create(int device) {
     for (int i = 0; i < 2; i++) { auto& m = e->msm_slot[i]; m.s = m.s2 = nullptr; m.fork = m.join = m.done = m.in = nullptr; m.ws = nullptr; m.ws_bytes = 0; m.seen_epoch = 0; }
     e->msm_seq = 0; e->cur_pipe = 0; e->ev_last_np = nullptr; e->np_epoch = 0; e->np_valid = 0;
     e->msm_pipeline = 0; e->halfagg_host_chain = 1; e->sync_split = 1; e->stage_log = 0;
-    e->msm_diag = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; e->msm_max_terms_opt = 0; e->musig_sum_fanin = 0;
+    e->msm_diag = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; e->msm_max_terms_opt = 0; e->musig_sum_fanin = 0; e->s2c_fused = 0;
     for (int i = 0; i < 2; i++) { e->rp_mem[i] = nullptr; e->ev_rp_fork[i] = e->ev_rp_join[i] = e->ev_rp_pre[i] = e->ev_rp_done[i] = nullptr; e->rp_done_valid[i] = 0; }
     e->rp_debug = 0;
     for (int i = 0; i < 2; i++) { auto& S = e->stage[i]; S.in = S.out = S.dev = nullptr; S.in_bytes = S.out_bytes = S.dev_bytes = 0; S.ev_h2d = S.ev_out = nullptr; S.used = 0; S.ticket = 0; S.sync_owned = 0; }
@@ -802,6 +802,30 @@ extern "C" int secp256k1_ecdsa_adaptor_verify_amd(const void* ctx, const unsigne
     if (!secp256k1_ecdsa_adaptor_verify_batch(e, &res, adaptor_sig162, (const unsigned char*)pubkey, msg32, (const unsigned char*)enckey, 1, 1)) return 0;
     return res;
 }
+// include/secp256k1_ecdsa_s2c.h (src/modules/ecdsa_s2c/main_impl.h:88 and :185) -- sig points at the 64-byte secp256k1_ecdsa_signature
+// object, pubkey and opening at 64-byte secp256k1_pubkey / secp256k1_ecdsa_s2c_opening objects (the kernels live in engine_s2c.hip)
+extern "C" int secp256k1_ecdsa_s2c_verify_commit_amd(const void* ctx, const void* sig, const unsigned char* data32, const void* opening) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!sig || !data32 || !opening) return s2k_fail_arg("secp256k1_ecdsa_s2c_verify_commit_amd", "illegal argument (ARG_CHECK)");
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0;
+    if (!secp256k1_ecdsa_s2c_verify_commit_batch(e, &res, (const unsigned char*)sig, nullptr, 1, data32, (const unsigned char*)opening, 1, 1)) return 0;
+    return res;
+}
+extern "C" int secp256k1_anti_exfil_host_verify_amd(const void* ctx, const void* sig, const unsigned char* msg32, const void* pubkey, const unsigned char* host_data32,
+                                                    const void* opening) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!sig || !msg32 || !pubkey || !host_data32 || !opening) return s2k_fail_arg("secp256k1_anti_exfil_host_verify_amd", "illegal argument (ARG_CHECK)");
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0;
+    if (!secp256k1_anti_exfil_host_verify_batch(e, &res, (const unsigned char*)sig, nullptr, 1, msg32, (const unsigned char*)pubkey, 1, host_data32,
+                                                (const unsigned char*)opening, 1, 1)) return 0;
+    return res;
+}
 // include/secp256k1_musig.h (src/modules/musig/session_impl.h:716) -- all five point at the reference's objects (the kernel lives in
 // engine_musig.hip)
 extern "C" int secp256k1_musig_partial_sig_verify_amd(const void* ctx, const void* partial_sig, const void* pubnonce, const void* pubkey, const void* keyagg_cache,
@@ -1012,6 +1036,7 @@ extern "C" int s2k_engine_set_option(s2k_engine* e, int option, long value) {
     case S2K_OPT_MUSIG_SUM_FANIN:
         if (value < 2 || value > 64) return s2k_fail_arg("s2k_engine_set_option", "S2K_OPT_MUSIG_SUM_FANIN: 2 .. 64");
         e->musig_sum_fanin = (int)value; return 1;
+    case S2K_OPT_S2C_FUSED: e->s2c_fused = value != 0; return 1;
     case S2K_OPT_GEN_CACHE_SLOTS: {                             // (the cache belongs to the device: every engine on it sees the change)
         s2k_dev_pool* p = e->pool;
         std::lock_guard<std::recursive_mutex> pool_lock(p->mu);
@@ -1303,6 +1328,47 @@ extern "C" int secp256k1_ecdsa_adaptor_verify_batch_group(s2k_group* g, int32_t*
     const int ok = group_run(g, jobs);
     if (!ok) memset(results, 0, sizeof(int32_t) * n);
     return ok;
+}
+// (split by item index as the ECDSA form; msghash32 == NULL: the commitment check alone)
+static int s2c_group_form(const char* who, s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format, const unsigned char* msghash32,
+                          const unsigned char* pubkeys, int pk_format, const unsigned char* data32, const unsigned char* openings, int opening_format, size_t n) {
+    if (sig_format < 0 || sig_format > 2 || pk_format < 0 || pk_format > 2 || opening_format < 0 || opening_format > 1) return s2k_fail_arg(who, "unknown sig_format / pk_format / opening_format");
+    std::lock_guard<std::mutex> call(g->call_mu);
+    memset(results, 0, sizeof(int32_t) * n);
+    const size_t k = g->eng.size(), pkb = pk_format == 0 ? 33 : pk_format == 1 ? 64 : 65, ob = opening_format ? 64 : 33;
+    const int der = sig_format == 2;
+    std::vector<std::function<int()>> jobs(k);
+    for (size_t i = 0; i < k; i++) {
+        size_t lo, hi; group_share(n, k, i, lo, hi);
+        s2k_engine* e = g->eng[i];
+        jobs[i] = [=]() -> int {
+            if (hi == lo) return 1;
+            if (!msghash32) return secp256k1_ecdsa_s2c_verify_commit_batch(e, results + lo, der ? sigs : sigs + 64 * lo, der ? sig_off + lo : nullptr, sig_format, data32 + 32 * lo,
+                                                                           openings + ob * lo, opening_format, hi - lo);
+            return secp256k1_anti_exfil_host_verify_batch(e, results + lo, der ? sigs : sigs + 64 * lo, der ? sig_off + lo : nullptr, sig_format, msghash32 + 32 * lo,
+                                                          pubkeys + pkb * lo, pk_format, data32 + 32 * lo, openings + ob * lo, opening_format, hi - lo);
+        };
+    }
+    const int ok = group_run(g, jobs);
+    if (!ok) memset(results, 0, sizeof(int32_t) * n);
+    return ok;
+}
+extern "C" int secp256k1_ecdsa_s2c_verify_commit_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
+                                                             const unsigned char* data32, const unsigned char* openings, int opening_format, size_t n) {
+    const char* who = "secp256k1_ecdsa_s2c_verify_commit_batch_group";
+    if (!g || g->eng.empty()) return s2k_fail(who, "null group");
+    if (n == 0) return 1;
+    if (!results || !sigs || !data32 || !openings || (sig_format == 2 && !sig_off)) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    return s2c_group_form(who, g, results, sigs, sig_off, sig_format, nullptr, nullptr, 0, data32, openings, opening_format, n);
+}
+extern "C" int secp256k1_anti_exfil_host_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
+                                                            const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format, const unsigned char* host_data32,
+                                                            const unsigned char* openings, int opening_format, size_t n) {
+    const char* who = "secp256k1_anti_exfil_host_verify_batch_group";
+    if (!g || g->eng.empty()) return s2k_fail(who, "null group");
+    if (n == 0) return 1;
+    if (!results || !sigs || !msghash32 || !pubkeys || !host_data32 || !openings || (sig_format == 2 && !sig_off)) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    return s2c_group_form(who, g, results, sigs, sig_off, sig_format, msghash32, pubkeys, pk_format, host_data32, openings, opening_format, n);
 }
 // (the items are shared out; every engine uploads the whole cache and session arrays, and session_of is checked here, once)
 extern "C" int secp256k1_musig_partial_sig_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* partial_sigs, int sig_format,
