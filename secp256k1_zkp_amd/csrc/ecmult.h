@@ -1222,8 +1222,13 @@ S2K_HD void ring_step_recode(u32 dw[9], u32& sneg, const half_scalar& h0, const 
 #endif
 }
 // FORM = 1: the three-base form (above): 2 doublings a level and its own recoding; the fields sit where the joint form's do.
-// FORM = 2: the six-base form: 1 doubling a level, one operand a level (field `level`), no lambda operand.
-template <int FORM>
+// FORM = 2: the six-base form: 1 doubling a level, one operand a level (field `level`), no lambda operand.  Its accumulator carries the signs
+//           its next operation wants (group.h: gej_dblneg_ring, gej_rsub_ge_ring, gez_add_ge_ring): a level is R <- -2R, R <- operand - R with
+//           -X handed back to the doubling; the table part runs on (-X, -Y, ZZ, ZZZ), which is where the hand-over leaves it once Z has
+//           changed sign with Y ((X, Y, Z) and (X, -Y, -Z) are one point).
+//           FRAC: R comes back as the fractions x = R.x / R.z, y = R.y / R.z (R.z = ZZ * ZZZ up to sign; a zero ZZ makes it zero), three
+//           products from the XYZZ accumulator, for a caller that inverts R.z and takes two more (rangeproof.h); otherwise as Jacobian.
+template <int FORM, bool FRAC = false>
 S2K_HD int ecmult_ring_step_t(gej& R, const u32* rtab, const scalar& e, const scalar& s, const scalar& f, int has_f, const u32* gtab, const u32* htab,
                               const s2k_lds_ptr dig) {
     constexpr bool TRIPLE = FORM == 1, SIX = FORM == 2;
@@ -1292,18 +1297,18 @@ S2K_HD int ecmult_ring_step_t(gej& R, const u32* rtab, const scalar& e, const sc
     if constexpr (SIX) {
 #pragma unroll
         for (int k = 0; k < 16; k++) raw[k] = nxt_addr[k];
-        gej_set_ge(R, cur);                                                 // level 0: the operand as it is
+        gej_set_ge(R, cur); fe_neg(R.x, R.x, 1);                            // level 0: the operand as it is, X carried as -X (2)
         au = 1;
         op_decode(cur, raw, nxt_neg, 0); cur_valid = nxt_valid;
         op_locate(nxt_addr, nxt_valid, nxt_neg, 2);
 #pragma unroll 1
         while (au < a_g0) {
             S2K_PROF_MARK(7);
-            gej_double_lean(R, R);
+            gej_dblneg_ring<true>(R, R);
             S2K_PROF_MARK(6);
 #pragma unroll
             for (int k = 0; k < 16; k++) raw[k] = nxt_addr[k];              // request the next record before the arithmetic
-            { const int same_x = gej_add_ge_lean(R, R, cur); if (S2K_WAVE_ANY(same_x)) return 0; }
+            { const int same_x = gej_rsub_ge_ring(R, R, cur); if (S2K_WAVE_ANY(same_x)) return 0; }
             au++;
             op_decode(cur, raw, nxt_neg, 0); cur_valid = nxt_valid;
             op_locate(nxt_addr, nxt_valid, nxt_neg, au + 1);
@@ -1344,7 +1349,14 @@ S2K_HD int ecmult_ring_step_t(gej& R, const u32* rtab, const scalar& e, const sc
     // table part (G, then H): a zero window adds nothing (per lane), so these additions are committed by select
 #if S2K_XYZZ_TABLE_PART
     gez acc4; acc4.inf = 0; acc4.x = R.x; acc4.y = R.y;
-    fe_sqr(acc4.zz, R.z); fe_mul(acc4.zzz, acc4.zz, R.z);
+    if constexpr (SIX) {                                                    // R = (-X, Y, Z) = (-X, -(-Y), -(-Z)): over -Z both coordinates are carried negated
+        fe nz; fe_neg(nz, R.z, 1);                                          // (2: squared as it is, 1*2 in the product)
+        fe_sqr(acc4.zz, nz); fe_mul(acc4.zzz, acc4.zz, nz);
+    } else {
+        fe_sqr(acc4.zz, R.z); fe_mul(acc4.zzz, acc4.zz, R.z);
+    }
+#else
+    if constexpr (SIX) { fe_neg(R.x, R.x, 1); fe_norm_weak(R.x); }
 #endif
     while (au < a_end) {
 #if S2K_NT_GTAB && defined(__HIP_DEVICE_COMPILE__)
@@ -1360,7 +1372,8 @@ S2K_HD int ecmult_ring_step_t(gej& R, const u32* rtab, const scalar& e, const sc
 #endif
 #if S2K_XYZZ_TABLE_PART
         {
-            gez t = acc4; gez_add_ge_lean(t, cur);
+            gez t = acc4;
+            if constexpr (SIX) gez_add_ge_ring(t, cur); else gez_add_ge_lean(t, cur);
             if (S2K_WAVE_ALL(cur_valid)) acc4 = t;               // (a zero digit -- one window value in 2^D -- is the only reason for the selects)
             else { fe_cmov(acc4.x, t.x, cur_valid); fe_cmov(acc4.y, t.y, cur_valid); fe_cmov(acc4.zz, t.zz, cur_valid); fe_cmov(acc4.zzz, t.zzz, cur_valid); }
         }
@@ -1375,7 +1388,18 @@ S2K_HD int ecmult_ring_step_t(gej& R, const u32* rtab, const scalar& e, const sc
     }
 #if S2K_XYZZ_TABLE_PART
     if (S2K_WAVE_ANY(fe_normalizes_to_zero(acc4.zz))) return 0;      // some committed addition met an operand with the accumulator's own x
-    gej_set_gez(R, acc4);
+    if constexpr (SIX) {
+        R.inf = 0;
+        if constexpr (FRAC) {                                           // x = X / ZZ = (-X) ZZZ / (-ZZ ZZZ), y = Y / ZZZ = (-Y) ZZ / (-ZZ ZZZ)
+            fe nzz; fe_neg(nzz, acc4.zz, 1);                            // (2)
+            fe_mul2(R.x, acc4.x, acc4.zzz, R.y, acc4.y, acc4.zz);       // (2*1, 1*1)
+            fe_mul(R.z, nzz, acc4.zzz);
+        } else {                                                        // (-X ZZ, -Y ZZZ, ZZ) with the two signs put right
+            fe_mul2(R.x, acc4.x, acc4.zz, R.y, acc4.y, acc4.zzz);
+            fe_neg(R.x, R.x, 1); fe_neg(R.y, R.y, 1); fe_norm_weak(R.x); fe_norm_weak(R.y);
+            R.z = acc4.zz;
+        }
+    } else gej_set_gez(R, acc4);
 #endif
     S2K_PROF_MARK(10);
 #ifdef S2K_ON_RING_STEP_DONE
@@ -1394,6 +1418,12 @@ S2K_HD int ecmult_ring3_step(gej& R, const u32* rtab, const scalar& e, const sca
 S2K_HD int ecmult_ring6_step(gej& R, const u32* rtab, const scalar& e, const scalar& s, const scalar& f, int has_f, const u32* gtab, const u32* htab,
                              const s2k_lds_ptr dig) {
     return ecmult_ring_step_t<2>(R, rtab, e, s, f, has_f, gtab, htab, dig);
+}
+// the same with R as the fractions over R.z (FRAC above; with the table part that is not on XYZZ there is nothing to take them from)
+#define S2K_RING6_FRAC (S2K_XYZZ_TABLE_PART != 0)
+S2K_HD int ecmult_ring6_step_frac(gej& R, const u32* rtab, const scalar& e, const scalar& s, const scalar& f, int has_f, const u32* gtab, const u32* htab,
+                                  const s2k_lds_ptr dig) {
+    return ecmult_ring_step_t<2, S2K_RING6_FRAC>(R, rtab, e, s, f, has_f, gtab, htab, dig);
 }
 
 

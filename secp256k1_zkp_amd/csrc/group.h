@@ -277,3 +277,74 @@ S2K_HD void gez_add_ge_lean(gez& a, const ge& b) {
     fe_mul2(a.zz, a.zz, pp, a.zzz, a.zzz, ppp);
     a.x = x3;
 }
+
+// ---- signed-accumulator forms of the rings' six-base step (ecmult.h: ecmult_ring_step_t<2>) and chain (rangeproof.h: rp_rings_shared) ----
+// The lean forms above carry X and Y with positive sign and then negate them -- and weakly normalise what the negation raised -- for the
+// differences of the formulas.  These carry the sign the NEXT operation wants, so that what is left is one negation in a doubling of the
+// chain, none in a doubling of a level, two in an addition, and only the normalisations a product's contract asks for (fe.h: magnitude
+// product <= 7, squaring input <= 2).  Same formulas, same field elements; points finite, no case analysis, as above.
+//
+// r = -2a: Z3 = y*Z, X3 = L^2 + 2T, and the fused line L (X3 + T) + S^2 IS -Y3, so it is left as it comes.  NX: a.x holds -X (a level of the
+// step: the addition below hands it over so) and T = (-X) S needs no negation either; otherwise a.x holds X (the chain).  L stays at magnitude 2:
+// it is squared (<= 2) and meets X3 + T (2) in the fused line, 2*2 + 1*1 = 5.
+// Magnitudes on entry: a.x <= 2 (NX) or 1, a.y <= 2, a.z 1; on exit: r.x 1 (holds +X3), r.y 1, r.z 1.
+template <bool NX>
+S2K_HD void gej_dblneg_ring(gej& r, const gej& a) {
+    fe l, s, t, w;
+    fe_mul_sqr(r.z, a.y, a.z, s, a.y);         // Z3 = y*Z (2*1), S = y^2 (mag 2 ok)           -> (1, 1)
+    if (NX) fe_mul_sqr(t, a.x, s, l, a.x);     // T = (-X)*S (2*1), X^2 (mag 2 ok)             -> (1, 1)
+    else { fe nx; fe_neg(nx, a.x, 1); fe_mul_sqr(t, nx, s, l, a.x); }      // -X               (2)
+    fe_mul_int(l, 3); fe_half(l);              // L = 3/2 X^2                                  (<= 2)
+    fe_sqr(r.x, l);                            // L^2 (mag 2 ok)                               (1)
+    fe_add(r.x, t); fe_add(r.x, t);            // X3 = L^2 + 2T                                (3)
+    fe_norm_weak(r.x);                         // (the next operation squares it or multiplies it)   (1)
+    fe_add2(w, r.x, t);                        // X3 + T                                       (2)
+    fe_muladd<false, true>(r.y, l, w, s, s);   // -Y3 = L*(X3+T) + S^2 : 2*2 + 1*1 <= 7        (1)
+    r.inf = 0;
+}
+// r = b - a (b affine, magnitudes (1, <= 2)), with r.x holding -X3; returns 1 iff a and b have the same x (then r is meaningless).  After
+// r = -2a above this is 2a + b.  a.y is -Y1 of the point added to, so i = S2 - Y1 is a sum of magnitude 2, which the squaring takes as it is,
+// and Y3 = i (t - X3) - Y1 h^3 = i (t + (-X3)) + a.y h^3 has both terms with the sign they come in.  h = U2 - X1 keeps its negation, its
+// exact normalisation and its zero test; the other negation is that of i^2.
+// Magnitudes on entry: a.x 1 (holds +X1), a.y 1, a.z 1; on exit: r.x 1 (holds -X3), r.y 1, r.z 1.
+S2K_HD int gej_rsub_ge_ring(gej& r, const gej& a, const ge& b) {
+    fe z12, u2, s2, h, i, h2, h3, t, i2, w;
+    fe_sqr(z12, a.z);
+    fe_mul2(u2, b.x, z12, s2, b.y, z12);       // U2 = x2*Z1^2, y2*Z1^2 (2*1)
+    fe_neg(h, a.x, 1); fe_add(h, u2);          // h = U2 - X1                                  (3)
+    fe_norm_seq(h);                            // exact limbs for the zero test, magnitude 1
+    fe_mul2(s2, s2, a.z, r.z, a.z, h);         // S2 = y2*Z1^3, Z3 = Z1*h
+    fe_add2(i, s2, a.y);                       // i = S2 - Y1                                  (2)
+    const int hz = fe_seq_is_zero(h);
+    fe_sqr2(i2, i, h2, h);                     // (mag 2 ok)
+    fe_mul2(h3, h, h2, t, a.x, h2);            // h^3, t = X1*h^2
+    fe_neg(w, i2, 1);                          // -i^2                                         (2)
+    fe_add(w, h3); fe_add(w, t); fe_add(w, t); // -X3 = h^3 + 2t - i^2                         (5)
+    fe_norm_weak(w);                           //                                              (1)
+    r.x = w;
+    fe_add(w, t);                              // t - X3                                       (2)
+    fe_muladd<false, false>(r.y, i, w, a.y, h3);   // Y3 = i*(t - X3) - Y1*h^3 : 2*2 + 1*1 <= 7    (1)
+    r.inf = 0;
+    return hz;
+}
+// The XYZZ addition with a.x = -X and a.y = -Y: P = U2 - X1 and R = S2 - Y1 are sums, R (magnitude 2) is squared as it is, -Q = (-X1) PP
+// comes out of the product, and -Y3 = R (X3 - Q) + (-Y1)(-PPP) is the fused line with both terms as they come.  Two negations are left
+// (PPP, X3) and two weak normalisations (P, whose square needs <= 2, and X3).
+// Magnitudes: a.x <= 2, a.y, a.zz, a.zzz 1 on entry and on exit; b.x 1, b.y <= 2.
+S2K_HD void gez_add_ge_ring(gez& a, const ge& b) {
+    fe u2, s2, p, r;
+    fe_mul2(u2, b.x, a.zz, s2, b.y, a.zzz);
+    fe_add2(p, u2, a.x); fe_norm_weak(p);                       // P = U2 - X1      (3 -> 1)
+    fe_add2(r, s2, a.y);                                        // R = S2 - Y1      (2)
+    fe pp, rr, ppp, nq;
+    fe_sqr2(pp, p, rr, r);                                      // (mag 2 ok)
+    fe_mul2(ppp, p, pp, nq, a.x, pp);                           // PPP, -Q = (-X1) PP (2*1)
+    fe x3, nppp, t1;
+    fe_neg(nppp, ppp, 1);                                       // -PPP             (2)
+    fe_add2(x3, rr, nppp); fe_add(x3, nq); fe_add(x3, nq);      // X3 = R^2 - PPP - 2Q (5)
+    fe_norm_weak(x3);                                           //                  (1)
+    fe_add2(t1, x3, nq);                                        // X3 - Q           (2)
+    fe_muladd<false, false>(a.y, r, t1, a.y, nppp);             // -Y3 = R (X3 - Q) + (-Y1)(-PPP): 2*2 + 1*2 = 6 <= 7, one reduction
+    fe_mul2(a.zz, a.zz, pp, a.zzz, a.zzz, ppp);
+    fe_neg(a.x, x3, 1);                                         // -X3              (2)
+}

@@ -540,13 +540,17 @@ S2K_HD int rp_ring_suspect(const gej& C, const u32* xmul /* this (exp, ring)'s 3
 #define S2K_RING_SIX 1
 #endif
 #if S2K_RING_TRIPLE && S2K_RING_SIX
-#define S2K_RP_RING_STEP ecmult_ring6_step
+#define S2K_RP_RING_STEP ecmult_ring6_step_frac         /* R as fractions over R.z where S2K_RING6_FRAC (ecmult.h) */
+#define S2K_RP_RING_FRAC S2K_RING6_FRAC
 #define S2K_RP_RING3_TABLES ecmult_ring6_tables
 #elif S2K_RING_TRIPLE
 #define S2K_RP_RING_STEP ecmult_ring3_step
 #define S2K_RP_RING3_TABLES ecmult_ring3_tables
 #else
 #define S2K_RP_RING_STEP ecmult_ring_step
+#endif
+#ifndef S2K_RP_RING_FRAC
+#define S2K_RP_RING_FRAC 0
 #endif
 #define RP_SHARED_SUSPECT 0
 #define RP_SHARED_SERVED 1
@@ -605,10 +609,19 @@ S2K_HD int rp_rings_shared(const rp_rec& rec, const u32* pub28, unsigned char* r
         gej T1;                                                     // T1 = 2^43 C, T = 2^86 C
 #pragma unroll 1
         for (int h = 0; h < 2; h++) {
+#if S2K_RING_SIX
+            // T <- -2T (group.h: gej_dblneg_ring; Y comes out at magnitude 1): 43 of them leave -2^43 C, whose y T1 takes negated (2), and 43
+            // more leave +2^86 C
+            const int nd = (dbg & 1u) ? 0 : 43;
+#pragma unroll 1
+            for (int k = 0; k < nd; k++) gej_dblneg_ring<false>(T, T);
+            if (h == 0) { T1 = T; if (nd) fe_neg(T1.y, T.y, 1); }
+#else
 #pragma unroll 1
             for (int k = 0; k < ((dbg & 1u) ? 0 : 43); k++) gej_double_lean(T, T);
             fe_norm_weak(T.y);
             if (h == 0) T1 = T;
+#endif
         }
         S2K_PROF_MARK(11);
         if (!(dbg & 2u)) S2K_RP_RING3_TABLES(M.rtab + (size_t)q * S2K_RTAB_WORDS, M.raw, C, T1, T);
@@ -657,7 +670,9 @@ S2K_HD int rp_rings_shared(const rp_rec& rec, const u32* pub28, unsigned char* r
             // goes back to the caller, i.e. to the general form, which starts the rings over on the keys themselves
             if (!S2K_WAVE_ALL(S2K_RP_RING_STEP(R, M.rtab + (size_t)q * S2K_RTAB_WORDS, ens, s, f, j > 0, gtab, htab, M.dig))) return RP_SHARED_EXCEPTIONAL;
             S2K_PROF_RESET;
-            fe_norm_weak(R.x); fe_norm_weak(R.y);
+#if !S2K_RP_RING_FRAC
+            fe_norm_weak(R.x); fe_norm_weak(R.y);                   // (the fractions are products as they come: magnitude 1)
+#endif
 #pragma unroll
             for (int i = 0; i < 9; i++) { pk(q, i) = R.x.n[i]; pk(q, 9 + i) = R.y.n[i]; pk(q, 18 + i) = R.z.n[i]; }
             pk(q, 36) = (u32)good;
@@ -698,8 +713,13 @@ S2K_HD int rp_rings_shared(const rp_rec& rec, const u32* pub28, unsigned char* r
                 fe x, y, zi, zi2, zi3;
 #pragma unroll
                 for (int i = 0; i < 9; i++) { x.n[i] = pk(q, i); y.n[i] = pk(q, 9 + i); zi.n[i] = pk(q, 18 + i); }
+#if S2K_RP_RING_FRAC
+                (void)zi2; (void)zi3;
+                fe_mul2(a.x, x, zi, a.y, y, zi);                    // the step left x and y as fractions over its third coordinate
+#else
                 fe_sqr(zi2, zi); fe_mul(zi3, zi2, zi);
                 fe_mul2(a.x, x, zi2, a.y, y, zi3);
+#endif
                 fe_normalize(a.x); fe_normalize(a.y);
             }
             int ok = (int)pk(q, 35);
