@@ -83,6 +83,9 @@ S2K_API void s2k_clear_status(void);
  * S2K_OPT_S2C_FUSED (default 0): secp256k1_anti_exfil_host_verify_batch runs the commitment check and the ECDSA verification in one kernel
  *   instead of the default chain of two (the commitment kernel's verdicts into a byte array, then an ECDSA kernel that ANDs them in).
  *   Results do not depend on it; the chain is the default because it measured faster (tools/s2c_bare.py).
+ * S2K_OPT_ELLSWIFT_MAX_ATTEMPTS (default and maximum 256, minimum 1): the bound of the rejection loop of secp256k1_ellswift_encode_batch.  An item
+ *   that finds no encoding within it gets results[i] = 0 and zero bytes and is counted (s2k_engine_ellswift_capped); at the default this is out
+ *   of reach of any input (about 1e-32 per item).  Smaller values exist for tests of the cap; the bytes of an item that succeeds do not depend on it.
  * Environment: only start-up defaults are read from it, once, when an engine (or the device's table pool) is created: S2K_DEVICE,
  * S2K_GEN_CACHE, S2K_GEN_CACHE_MIN, S2K_STAGE_THREADS, S2K_GTAB_BITS.  Nothing on a call path reads the environment. */
 #define S2K_OPT_RP_INPUTS_READY 1
@@ -98,6 +101,7 @@ S2K_API void s2k_clear_status(void);
 #define S2K_OPT_GTAB_BITS 11
 #define S2K_OPT_MUSIG_SUM_FANIN 12
 #define S2K_OPT_S2C_FUSED 13
+#define S2K_OPT_ELLSWIFT_MAX_ATTEMPTS 14
 S2K_API int s2k_engine_set_option(s2k_engine* e, int option, long value);
 /* Rangeproof generator tables.  The four public keys of a Borromean ring differ by multiples of the proof's generator
  * (secp256k1_rangeproof_pub_expand, src/modules/rangeproof/rangeproof_impl.h:19-51), so when the engine holds a fixed-base table of that
@@ -270,6 +274,34 @@ S2K_API int secp256k1_anti_exfil_host_verify_batch_dev(s2k_engine* e, void* stre
                                                        const unsigned char* host_data32, const unsigned char* openings, int opening_format, size_t n);
 S2K_API int secp256k1_ecdsa_anti_exfil_host_commit_batch(s2k_engine* e, unsigned char* commitments_out32, const unsigned char* rand32, size_t n);
 S2K_API int secp256k1_ecdsa_anti_exfil_host_commit_batch_dev(s2k_engine* e, void* stream, unsigned char* commitments_out32, const unsigned char* rand32, size_t n);
+
+/* ---- ElligatorSwift (BIP-324): batch decoding and encoding of public keys ------------------------------------------------
+ * decode:  out_i = what secp256k1_ellswift_decode(ctx, ., ell64 + 64 i) writes
+ *                                       (include/secp256k1_ellswift.h, src/modules/ellswift/main_impl.h:470-483; the map:
+ *                                        secp256k1_ellswift_xswiftec_frac_var :24-132)
+ *          out_format 0: n*32, ser32(x) alone (secp256k1_ellswift_xswiftec_var :135-140; no root for y is taken)
+ *                     1: n*64 secp256k1_pubkey objects, byte for byte the reference's
+ *                     2: n*33 compressed keys (what secp256k1_ec_pubkey_serialize makes of those objects)
+ *          Every 64 bytes decode (u and t >= p are reduced, not refused), so there is no results array and the call returns 1.
+ * encode:  results[i], ell64_out + 64 i = what the key parser + secp256k1_ellswift_encode(ctx, ., key_i, rnd32 + 32 i) give
+ *                                       (src/modules/ellswift/main_impl.h:393-420; the loop: :333-382; the partial inverse: :168-303)
+ *          key_format 1: n*64 secp256k1_pubkey objects; 2: n*33 compressed keys, accepted and refused as secp256k1_ec_pubkey_parse does.
+ *          results[i] = 0 and 64 zero bytes for a refused key and for the all-zero object (the reference: illegal-argument callback,
+ *          0, zeros); the neighbours are not affected.  rnd32 is PUBLIC randomness: nothing here is constant time.
+ *          The one deviation from the reference: its loop runs until it succeeds, the engine's stops after 256 attempts
+ *          (S2K_OPT_ELLSWIFT_MAX_ATTEMPTS; about 1/4 of the attempts succeed, so no input gets there: (3/4)^256 ~ 1e-32).  Such an item
+ *          gets results[i] = 0 and zero bytes, and s2k_engine_ellswift_capped() counts it.
+ * NULL where the reference has ARG_CHECK, or a format out of range, is S2K_STATUS_ILLEGAL_ARGUMENT (return 0); n == 0 returns 1.  The
+ * _dev forms take device pointers and zero their outputs on the stream first.
+ * secp256k1_ellswift_create and secp256k1_ellswift_xdh handle a secret key and need the reference's constant-time code. */
+S2K_API int secp256k1_ellswift_decode_batch(s2k_engine* e, unsigned char* out, int out_format, const unsigned char* ell64, size_t n);
+S2K_API int secp256k1_ellswift_decode_batch_dev(s2k_engine* e, void* stream, unsigned char* out, int out_format, const unsigned char* ell64, size_t n);
+S2K_API int secp256k1_ellswift_encode_batch(s2k_engine* e, int32_t* results, unsigned char* ell64_out, const unsigned char* keys, int key_format,
+                                            const unsigned char* rnd32, size_t n);
+S2K_API int secp256k1_ellswift_encode_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* ell64_out, const unsigned char* keys, int key_format,
+                                                const unsigned char* rnd32, size_t n);
+/* *count = the items of this engine's encode calls that have hit the attempt cap since the engine was created.  Waits for the device. */
+S2K_API int s2k_engine_ellswift_capped(s2k_engine* e, uint64_t* count);
 
 /* ---- MuSig2: batch partial-signature verification and nonce processing (the coordinator's half) ------------------------
  * results[i] = inputs parse &&
@@ -635,6 +667,12 @@ S2K_API int secp256k1_ecdsa_adaptor_verify_amd(const void* ctx, const unsigned c
 S2K_API int secp256k1_ecdsa_s2c_verify_commit_amd(const void* ctx, const void* sig, const unsigned char* data32, const void* opening);
 S2K_API int secp256k1_anti_exfil_host_verify_amd(const void* ctx, const void* sig, const unsigned char* msg32, const void* pubkey, const unsigned char* host_data32,
                                                  const void* opening);
+/*   secp256k1_ellswift_decode(ctx, pubkey, ell64)                                      include/secp256k1_ellswift.h,
+ *                                                                                      src/modules/ellswift/main_impl.h:470
+ *   secp256k1_ellswift_encode(ctx, ell64, pubkey, rnd32)                               src/modules/ellswift/main_impl.h:393
+ * pubkey: the 64-byte secp256k1_pubkey object.  decode returns 1 (0 + S2K_STATUS_ENGINE_FAILURE and a zeroed object when the engine failed). */
+S2K_API int secp256k1_ellswift_decode_amd(const void* ctx, void* pubkey, const unsigned char* ell64);
+S2K_API int secp256k1_ellswift_encode_amd(const void* ctx, unsigned char* ell64, const void* pubkey, const unsigned char* rnd32);
 /*   secp256k1_musig_partial_sig_verify(ctx, partial_sig, pubnonce, pubkey, keyagg_cache, session)      include/secp256k1_musig.h,
  *                                                                                      src/modules/musig/session_impl.h:716
  * all five point at the reference's objects (36, 132, 64, 197 and 133 bytes). */
@@ -785,6 +823,7 @@ S2K_API int secp256k1_ecdsa_s2c_verify_commit_batch_group(s2k_group* g, int32_t*
 S2K_API int secp256k1_anti_exfil_host_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
                                                          const unsigned char* msghash32, const unsigned char* pubkeys, int pk_format, const unsigned char* host_data32,
                                                          const unsigned char* openings, int opening_format, size_t n);
+S2K_API int secp256k1_ellswift_decode_batch_group(s2k_group* g, unsigned char* out, int out_format, const unsigned char* ell64, size_t n);
 /* (every engine gets its share of the items and the whole cache / session arrays) */
 S2K_API int secp256k1_musig_partial_sig_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* partial_sigs, int sig_format,
                                                            const unsigned char* pubnonces, int nonce_format, const unsigned char* pubkeys, int pk_format,

@@ -106,6 +106,14 @@ SIGNATURES = {
     "secp256k1_anti_exfil_host_verify_batch_group": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_s2c_verify_commit_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "secp256k1_anti_exfil_host_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "secp256k1_ellswift_decode_batch": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_ellswift_decode_batch_dev": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_ellswift_encode_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_ellswift_encode_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_ellswift_decode_batch_group": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_ellswift_decode_amd": (_c.c_int, [_vp, _vp, _vp]),
+    "secp256k1_ellswift_encode_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
+    "s2k_engine_ellswift_capped": (_c.c_int, [_vp, _vp]),
     "secp256k1_musig_partial_sig_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "secp256k1_musig_pubkey_agg_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _sz]),
     "secp256k1_whitelist_verify_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _vp]),

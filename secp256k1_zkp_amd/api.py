@@ -122,6 +122,29 @@ def _s2c_args(what, sigs, data32, openings, sig_format, opening_format, msghashe
 
 
 _TWEAK_KEY_BYTES = {0: 32, 1: 64, 2: 33}     # serialised x-only / secp256k1_xonly_pubkey or secp256k1_pubkey object / compressed
+_ELLSWIFT_OUT_BYTES = {0: 32, 1: 64, 2: 33}  # ser32(x) / secp256k1_pubkey object / compressed
+
+
+def _ellswift_decode_args(what, ell64, out_format):
+    """shape checks shared by the ElligatorSwift decode methods of Engine and Group; returns (ell64, n)"""
+    if out_format not in _ELLSWIFT_OUT_BYTES:
+        raise ValueError(f"{what}: out_format must be 0 (x only), 1 (key objects) or 2 (compressed keys)")
+    if ell64 is None:
+        raise ValueError(f"{what}: missing array")
+    ell64 = _u8(ell64); n = ell64.size // 64
+    _need(what + " ell64", ell64, 64 * n)
+    return ell64, n
+
+
+def _ellswift_encode_args(what, keys, key_format, rnd32):
+    """returns (keys, rnd32, n)"""
+    if key_format not in (1, 2):
+        raise ValueError(f"{what}: key_format must be 1 (n*64 key objects) or 2 (n*33 compressed keys)")
+    if keys is None or rnd32 is None:
+        raise ValueError(f"{what}: missing array")
+    keys = _u8(keys); rnd32 = _u8(rnd32); n = keys.size // _TWEAK_KEY_BYTES[key_format]
+    _need(what + " keys", keys, _TWEAK_KEY_BYTES[key_format] * n); _need(what + " rnd32", rnd32, 32 * n)
+    return keys, rnd32, n
 
 
 def _tweak_check_args(what, tweaked32, parities, internal_keys, tweaks32, key_format):
@@ -177,6 +200,7 @@ class Engine:
     OPT_GTAB_BITS = 11
     OPT_MUSIG_SUM_FANIN = 12
     OPT_S2C_FUSED = 13
+    OPT_ELLSWIFT_MAX_ATTEMPTS = 14
 
     def cache_generator(self, gen64):
         """Build the fixed-base table of one rangeproof generator now (s2k_engine_cache_generator)."""
@@ -575,6 +599,40 @@ class Engine:
         n = tweaks32.numel() // 32 if n is None else n
         self._check(self._lib.secp256k1_pubkey_tweak_add_batch_dev(self._h, stream, _dp(results), _dp(pubkeys_out64), _dp(keys), key_format, _dp(tweaks32), n),
                     "secp256k1_pubkey_tweak_add_batch_dev")
+
+    # ---- secp256k1_ellswift_decode and secp256k1_ellswift_encode (modules/ellswift/main_impl.h:470-483, :393-420), batched ----
+    def ellswift_decode(self, ell64, out_format=1):
+        """ell64: n*64 ElligatorSwift encodings -> out[n, 32 / 64 / 33]: out_format 0: ser32(x), 1: secp256k1_pubkey objects, 2: compressed keys.
+        Every input decodes."""
+        ell64, n = _ellswift_decode_args("ellswift_decode", ell64, out_format)
+        out = np.zeros((n, _ELLSWIFT_OUT_BYTES[out_format]), np.uint8)
+        self._check(self._lib.secp256k1_ellswift_decode_batch(self._h, _p(out), out_format, _p(ell64), n), "secp256k1_ellswift_decode_batch")
+        return out
+
+    def ellswift_decode_dev(self, out, ell64, out_format=1, n=None, stream=None):
+        """every array in HBM (torch tensors)"""
+        n = ell64.numel() // 64 if n is None else n
+        self._check(self._lib.secp256k1_ellswift_decode_batch_dev(self._h, stream, _dp(out), out_format, _dp(ell64), n), "secp256k1_ellswift_decode_batch_dev")
+
+    def ellswift_encode(self, keys, rnd32, key_format=1):
+        """keys: key_format 1: n*64 secp256k1_pubkey objects, 2: n*33 compressed keys; rnd32: n*32 bytes of PUBLIC randomness
+        -> (results[n], ell64[n, 64]), zero where results[i] == 0 (a refused key, or the attempt cap: ellswift_capped())"""
+        keys, rnd32, n = _ellswift_encode_args("ellswift_encode", keys, key_format, rnd32)
+        res = np.zeros(n, np.int32); out = np.zeros((n, 64), np.uint8)
+        self._check(self._lib.secp256k1_ellswift_encode_batch(self._h, _p(res), _p(out), _p(keys), key_format, _p(rnd32), n), "secp256k1_ellswift_encode_batch")
+        return res, out
+
+    def ellswift_encode_dev(self, results, ell64_out, keys, rnd32, key_format=1, n=None, stream=None):
+        """every array in HBM (torch tensors)"""
+        n = rnd32.numel() // 32 if n is None else n
+        self._check(self._lib.secp256k1_ellswift_encode_batch_dev(self._h, stream, _dp(results), _dp(ell64_out), _dp(keys), key_format, _dp(rnd32), n),
+                    "secp256k1_ellswift_encode_batch_dev")
+
+    def ellswift_capped(self):
+        """items of this engine's encode calls that hit the attempt cap so far (s2k_engine_ellswift_capped; waits for the device)"""
+        c = ctypes.c_uint64(0)
+        self._check(self._lib.s2k_engine_ellswift_capped(self._h, ctypes.byref(c)), "s2k_engine_ellswift_capped")
+        return int(c.value)
 
     # ---- secp256k1_generator_generate[_blinded] / _parse / _serialize and secp256k1_pedersen_commit (modules/generator/main_impl.h:59-335), batched.
     #      Public inputs only: blinds are treated as public data (nothing is constant time). ----
@@ -1035,6 +1093,12 @@ class Group:
         self._check(self._lib.secp256k1_anti_exfil_host_verify_batch_group(self._h, _p(res), _p(sigs), _p(off), sig_format, _p(msghashes), _p(pubkeys), pk_format,
                                                                            _p(host_data32), _p(openings), opening_format, n), "secp256k1_anti_exfil_host_verify_batch_group")
         return res
+
+    def ellswift_decode(self, ell64, out_format=1):
+        ell64, n = _ellswift_decode_args("ellswift_decode_group", ell64, out_format)
+        out = np.zeros((n, _ELLSWIFT_OUT_BYTES[out_format]), np.uint8)
+        self._check(self._lib.secp256k1_ellswift_decode_batch_group(self._h, _p(out), out_format, _p(ell64), n), "secp256k1_ellswift_decode_batch_group")
+        return out
 
     def xonly_tweak_add_check_batch(self, tweaked32, parities, internal_keys, tweaks32, key_format=0):
         tweaked32, parities, internal_keys, tweaks32, n = _tweak_check_args("xonly_tweak_add_check_batch_group", tweaked32, parities, internal_keys, tweaks32, key_format)

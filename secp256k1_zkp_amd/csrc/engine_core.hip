@@ -445,7 +445,7 @@ extern "C" s2k_engine* s2k_engine_create(int device) {
     for (int i = 0; i < 2; i++) { auto& m = e->msm_slot[i]; m.s = m.s2 = nullptr; m.fork = m.join = m.done = m.in = nullptr; m.ws = nullptr; m.ws_bytes = 0; m.seen_epoch = 0; }
     e->msm_seq = 0; e->cur_pipe = 0; e->ev_last_np = nullptr; e->np_epoch = 0; e->np_valid = 0;
     e->msm_pipeline = 0; e->halfagg_host_chain = 1; e->sync_split = 1; e->stage_log = 0;
-    e->msm_diag = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; e->msm_max_terms_opt = 0; e->musig_sum_fanin = 0; e->s2c_fused = 0;
+    e->msm_diag = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; e->msm_max_terms_opt = 0; e->musig_sum_fanin = 0; e->s2c_fused = 0; e->ellswift_max_attempts = 256;
     for (int i = 0; i < 2; i++) { e->rp_mem[i] = nullptr; e->ev_rp_fork[i] = e->ev_rp_join[i] = e->ev_rp_pre[i] = e->ev_rp_done[i] = nullptr; e->rp_done_valid[i] = 0; }
     e->rp_debug = 0;
     for (int i = 0; i < 2; i++) { auto& S = e->stage[i]; S.in = S.out = S.dev = nullptr; S.in_bytes = S.out_bytes = S.dev_bytes = 0; S.ev_h2d = S.ev_out = nullptr; S.used = 0; S.ticket = 0; S.sync_owned = 0; }
@@ -826,6 +826,31 @@ extern "C" int secp256k1_anti_exfil_host_verify_amd(const void* ctx, const void*
                                                 (const unsigned char*)opening, 1, 1)) return 0;
     return res;
 }
+// include/secp256k1_ellswift.h (src/modules/ellswift/main_impl.h:470 and :393) -- pubkey points at the 64-byte secp256k1_pubkey object (the
+// kernels live in engine_ellswift.hip)
+extern "C" int secp256k1_ellswift_decode_amd(const void* ctx, void* pubkey, const unsigned char* ell64) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!pubkey) return s2k_fail_arg("secp256k1_ellswift_decode_amd", "illegal argument (ARG_CHECK)");
+    memset(pubkey, 0, 64);
+    if (!ell64) return s2k_fail_arg("secp256k1_ellswift_decode_amd", "illegal argument (ARG_CHECK)");
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    if (!secp256k1_ellswift_decode_batch(e, (unsigned char*)pubkey, 1, ell64, 1)) { memset(pubkey, 0, 64); return 0; }
+    return 1;
+}
+extern "C" int secp256k1_ellswift_encode_amd(const void* ctx, unsigned char* ell64, const void* pubkey, const unsigned char* rnd32) {
+    (void)ctx;
+    s2k_clear_status();
+    if (!ell64) return s2k_fail_arg("secp256k1_ellswift_encode_amd", "illegal argument (ARG_CHECK)");
+    memset(ell64, 0, 64);
+    if (!pubkey || !rnd32) return s2k_fail_arg("secp256k1_ellswift_encode_amd", "illegal argument (ARG_CHECK)");
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0;
+    if (!secp256k1_ellswift_encode_batch(e, &res, ell64, (const unsigned char*)pubkey, 1, rnd32, 1)) { memset(ell64, 0, 64); return 0; }
+    return res;
+}
 // include/secp256k1_musig.h (src/modules/musig/session_impl.h:716) -- all five point at the reference's objects (the kernel lives in
 // engine_musig.hip)
 extern "C" int secp256k1_musig_partial_sig_verify_amd(const void* ctx, const void* partial_sig, const void* pubnonce, const void* pubkey, const void* keyagg_cache,
@@ -1037,6 +1062,9 @@ extern "C" int s2k_engine_set_option(s2k_engine* e, int option, long value) {
         if (value < 2 || value > 64) return s2k_fail_arg("s2k_engine_set_option", "S2K_OPT_MUSIG_SUM_FANIN: 2 .. 64");
         e->musig_sum_fanin = (int)value; return 1;
     case S2K_OPT_S2C_FUSED: e->s2c_fused = value != 0; return 1;
+    case S2K_OPT_ELLSWIFT_MAX_ATTEMPTS:
+        if (value < 1 || value > 256) return s2k_fail_arg("s2k_engine_set_option", "S2K_OPT_ELLSWIFT_MAX_ATTEMPTS: 1 .. 256");
+        e->ellswift_max_attempts = (int)value; return 1;
     case S2K_OPT_GEN_CACHE_SLOTS: {                             // (the cache belongs to the device: every engine on it sees the change)
         s2k_dev_pool* p = e->pool;
         std::lock_guard<std::recursive_mutex> pool_lock(p->mu);
@@ -1369,6 +1397,26 @@ extern "C" int secp256k1_anti_exfil_host_verify_batch_group(s2k_group* g, int32_
     if (n == 0) return 1;
     if (!results || !sigs || !msghash32 || !pubkeys || !host_data32 || !openings || (sig_format == 2 && !sig_off)) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     return s2c_group_form(who, g, results, sigs, sig_off, sig_format, msghash32, pubkeys, pk_format, host_data32, openings, opening_format, n);
+}
+// (split by item index; every engine decodes its share into its slice of `out`)
+extern "C" int secp256k1_ellswift_decode_batch_group(s2k_group* g, unsigned char* out, int out_format, const unsigned char* ell64, size_t n) {
+    const char* who = "secp256k1_ellswift_decode_batch_group";
+    if (!g || g->eng.empty()) return s2k_fail(who, "null group");
+    if (n == 0) return 1;
+    if (!out || !ell64) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    if (out_format < 0 || out_format > 2) return s2k_fail_arg(who, "out_format must be 0 (n*32 x only), 1 (n*64 objects) or 2 (n*33 compressed)");
+    std::lock_guard<std::mutex> call(g->call_mu);
+    const size_t k = g->eng.size(), ob = out_format == 0 ? 32 : out_format == 1 ? 64 : 33;
+    memset(out, 0, ob * n);
+    std::vector<std::function<int()>> jobs(k);
+    for (size_t i = 0; i < k; i++) {
+        size_t lo, hi; group_share(n, k, i, lo, hi);
+        s2k_engine* e = g->eng[i];
+        jobs[i] = [=]() -> int { return hi == lo ? 1 : secp256k1_ellswift_decode_batch(e, out + ob * lo, out_format, ell64 + 64 * lo, hi - lo); };
+    }
+    const int ok = group_run(g, jobs);
+    if (!ok) memset(out, 0, ob * n);
+    return ok;
 }
 // (the items are shared out; every engine uploads the whole cache and session arrays, and session_of is checked here, once)
 extern "C" int secp256k1_musig_partial_sig_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* partial_sigs, int sig_format,

@@ -1,7 +1,7 @@
 // engine_internal.h -- what the translation units of the gfx950 batch-verification engine share (see include/secp256k1_zkp_amd.h):
 // the engine object, the per-device table pool, error plumbing, workspace carving and the host functions one kernel family offers the others.
 //
-// The library is fifteen translation units, one per kernel family, compiled separately (hipcc --offload-arch=gfx950 -O3 -fPIC -c) and linked
+// The library is sixteen translation units, one per kernel family, compiled separately (hipcc --offload-arch=gfx950 -O3 -fPIC -c) and linked
 // into one shared object (see __graft_entry__.build):
 //   engine_core.hip        table construction, the per-device pool and generator-table cache, engine lifecycle / options / groups,
 //                          s2k_ecmult_batch, BIP-340, the single-item `_amd` forms and the `_group` forms of every family
@@ -19,6 +19,7 @@
 //   engine_musig.hip       MuSig2 partial-signature verification and nonce processing (musig.h)
 //   engine_musig_agg.hip   MuSig2 key aggregation, cache tweaks, nonce aggregation and signature aggregation (musig_agg.h)
 //   engine_s2c.hip         ECDSA sign-to-contract checks, anti-exfil host verification and host commitments (s2c.h)
+//   engine_ellswift.hip    ElligatorSwift decoding and encoding of public keys (ellswift.h)
 // The per-lane arithmetic lives in the headers next to these files.  No device function is called across translation units (no -fgpu-rdc):
 // a family that needs another family's kernels calls the HOST function that launches them.
 // There is no CPU implementation behind the entry points: without a HIP device every call fails loudly.
@@ -93,7 +94,7 @@ struct s2k_engine {
     int rp_debug;              // diagnostic launches ($S2K_RP_DEBUG: rp_rings_shared's dbg bits; results are meaningless then)
     int rp_inputs_ready;       // S2K_OPT_RP_INPUTS_READY: the side-stream stage need not wait for earlier work of the caller's stream
     u32* host_flags;           // pinned, 64 bytes (diagnostic read-backs)
-    u32* dev_flags;            // device, 64 bytes: [0] the most recent MSM launch overflowed a bucket region (exact path taken)
+    u32* dev_flags;            // device, 64 bytes: [0] the most recent MSM launch overflowed a bucket region (exact path taken); [1] items of ElligatorSwift encode calls that hit the attempt cap
     std::vector<unsigned char> bp_key;   // serialised generator set the BP++ fixed-base table was built for
     u32* bp_tab; size_t bp_tab_bytes, bp_tab_stride;   // the BP++ generator set's fixed-base tables (bppp.h: one table of G's format per generator, bp_tab_stride words apart), kept across calls
     int bp_gens_ok;            // every generator of the cached set parsed (what k_bp_gens found when the table was built)
@@ -137,6 +138,7 @@ struct s2k_engine {
     size_t msm_max_terms_opt;  // S2K_OPT_MSM_MAX_TERMS: sums with more terms go as several launches whose partial sums add (0: the 32-bit reference limit)
     int musig_sum_fanin;       // S2K_OPT_MUSIG_SUM_FANIN: partials one lane of the MuSig summing kernel folds per pass (0: the default, 64)
     int s2c_fused;             // S2K_OPT_S2C_FUSED: anti-exfil host verification as one kernel instead of the default chain of two (engine_s2c.hip)
+    int ellswift_max_attempts; // S2K_OPT_ELLSWIFT_MAX_ATTEMPTS: the bound of the ElligatorSwift encode loop (engine_ellswift.hip; default and maximum 256)
     u32* ha_pin; size_t ha_pin_words;   // pinned: the chain states of the half-aggregate randomizer hash, walked on the host (host_sha256.h)
     // Buffers this engine has outgrown.  Growing a buffer never waits for the device (round 6; it used to be hipDeviceSynchronize() + hipFree
     // under the engine's lock, i.e. a stall for the longest stream of EVERY engine on the GPU): the new buffer is allocated beside the old
