@@ -576,6 +576,47 @@ S2K_API int secp256k1_schnorrsig_inc_aggregate_batch_dev(s2k_engine* e, void* st
                                                          const uint64_t* n_before, const unsigned char* pubkeys, int pk_format, const unsigned char* msgs32,
                                                          const unsigned char* new_sigs64, const uint64_t* item_off, size_t n_aggs);
 
+/* ---- BIP-340: one verdict for a whole batch, as a single multi-scalar multiplication ------------------------------------------
+ * *verdict = AND over i of secp256k1_schnorrsig_verify(ctx, sig64_i, msg_i, msglen, pubkey_i)
+ *                                       (include/secp256k1_schnorrsig.h, src/modules/schnorrsig/main_impl.h:215-261; challenge :106-120)
+ * The reference has no batch verifier; this is the one BIP-340 describes.  For a block validator or an indexer that only needs to know
+ * whether ALL signatures are valid:  -(sum a_i s_i) G + sum a_i R_i + sum (a_i e_i) P_i == infinity,  R_i = lift_x(r_i), one
+ * (2n+1)-term sum (points R_0, P_0, R_1, P_1, ... as in the half-aggregate verifier) instead of n double multiplications.
+ * The verdict is 0 whenever some r_i >= p, r_i is not an x coordinate, s_i >= n or a key does not parse (an all-zero key object
+ * included) -- the refusals of :231-242, and an r_i that no R can match (:260) -- and otherwise 1 exactly when the equation holds.  A batch of valid signatures is never
+ * refused; a batch holding an invalid one is accepted with probability at most 2^-128 over the hash that gives the coefficients.
+ *
+ * The coefficients a_i come from the batch itself through a hash TREE (16 children per node, one GPU lane per node, one launch per
+ * level), so that every a_i depends on every byte of the batch and nothing is serial beyond the tree's depth:
+ *   T(tag, x) = SHA256(SHA256(tag) | SHA256(tag) | x)
+ *   d_i  = T("S2K/schnorr_all/item", sig_i | x32_i | m_i)      x32_i: the key's 32 serialised bytes (pk_format 1: the object's x, big-endian)
+ *   node j of the next level = T("S2K/schnorr_all/node", nodes 16j .. min(16j+16, count)-1 of this level), from d_0 .. d_{n-1} until one is left
+ *   seed = T("S2K/schnorr_all/seed", le64(n) | le64(msglen) | root)                                (n = 1: root = d_0)
+ *   a_0 = 1;  a_i = the first 16 bytes, big-endian, of T("S2K/schnorr_all/rand", seed | le64(i)), 0 replaced by 1
+ * seed32_out (or NULL) receives the seed: it pins the derivation for tests and lets two parties compare what they verified.
+ *
+ * sigs n*64, msgs n*msglen (msglen uniform, may be 0), pubkeys / pk_format as in secp256k1_schnorrsig_verify_batch (0 = n*32
+ * serialised x-only keys, 1 = n*64 secp256k1_xonly_pubkey objects).  The return value is the call's success, the verdict goes to
+ * *verdict.  NULL where the reference has ARG_CHECK, or a pk_format out of range, is S2K_STATUS_ILLEGAL_ARGUMENT (return 0), and so
+ * is a batch of more terms than one sum indexes (2n + 1 above 238 609 293, or S2K_OPT_MSM_MAX_TERMS: "batch too large").
+ * n == 0 returns 1 with verdict 1 and 32 zero bytes as the seed.
+ * results (n entries, or NULL), host form only: when the verdict is 0 the per-item verifier (secp256k1_schnorrsig_verify_batch_dev)
+ * runs on the buffers already uploaded and results[] says which items failed; when it is 1 results[] is all ones.
+ * The _dev form: every array in HBM, stream-ordered, never synchronises and writes only verdict_dev[0] and, if asked for, the 32
+ * seed bytes; a caller that wants locations calls secp256k1_schnorrsig_verify_batch_dev itself.
+ * Timing.  s2k_engine_last_ms(0) spans the call's launches (after a locating host call: the per-item verifier's), s2k_engine_last_ms(1)
+ * is the multi-scalar multiplication.  s2k_schnorr_all_last_split_ms: the phases of the most recent call of the engine, in ms, valid
+ * once its work is complete -- out4[0] lift, item digests and challenges, [1] hash tree and seed, [2] coefficients, scalar products
+ * and the sum of a_i s_i, [3] the multi-scalar multiplication; -1 where there is nothing to report.
+ *
+ * Out of scope: group forms, the hook into the reference's own functions (integration/), bench.py, several batches per call,
+ * Taproot tweak checks inside the batch, caller-supplied randomness, and automatic dispatch between this call and the per-item one. */
+S2K_API int secp256k1_schnorrsig_verify_all(s2k_engine* e, int32_t* verdict, int32_t* results, unsigned char* seed32_out, const unsigned char* sigs,
+                                            const unsigned char* msgs, size_t msglen, const unsigned char* pubkeys, int pk_format, size_t n);
+S2K_API int secp256k1_schnorrsig_verify_all_dev(s2k_engine* e, void* stream, int32_t* verdict_dev, unsigned char* seed32_out_dev, const unsigned char* sigs,
+                                                const unsigned char* msgs, size_t msglen, const unsigned char* pubkeys, int pk_format, size_t n);
+S2K_API int s2k_schnorr_all_last_split_ms(s2k_engine* e, float* out4);
+
 /* ---- Borromean rangeproof batch verification ---------------------------------------------------------------------
  * results[i], min_value[i], max_value[i] = secp256k1_rangeproof_verify(ctx, &min, &max, commit_i, proof_i, plen_i,
  *                                          extra_commit_i, extra_commit_len_i, gen_i)

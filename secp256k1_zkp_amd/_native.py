@@ -44,6 +44,9 @@ SIGNATURES = {
     "s2k_ecmult_multi_window_partial_dev": (_c.c_int, [_vp, _vp] + [_vp] * 5 + [_sz, _c.c_uint32, _c.c_uint32]),
     "secp256k1_schnorrsig_verify_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _c.c_int, _sz]),
     "secp256k1_schnorrsig_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _c.c_int, _sz]),
+    "secp256k1_schnorrsig_verify_all": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _c.c_int, _sz]),
+    "secp256k1_schnorrsig_verify_all_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _c.c_int, _sz]),
+    "s2k_schnorr_all_last_split_ms": (_c.c_int, [_vp, _vp]),
     "secp256k1_ecdsa_verify_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_recover_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz]),

@@ -325,6 +325,44 @@ class Engine:
         self._check(self._lib.secp256k1_schnorrsig_verify_batch_dev(self._h, stream, _dp(results), _dp(sigs), _dp(msgs), msglen, _dp(pubkeys),
                                                                     pk_format, n), "secp256k1_schnorrsig_verify_batch_dev")
 
+    # ---- one verdict for a whole batch of BIP-340 signatures, as a single multi-scalar multiplication (csrc/schnorr_all.h) ----
+    def schnorrsig_verify_all(self, sigs, msgs, pubkeys, msglen=32, pk_format=0, locate=False, want_seed=False):
+        """1 exactly when every signature of the batch verifies.  Returns the verdict; with locate=True (verdict, results) where results
+        are the per-item verdicts (all ones when the verdict is 1); with want_seed=True the 32-byte seed of the coefficients is appended."""
+        if pk_format not in (0, 1):
+            raise ValueError("schnorrsig_verify_all: pk_format must be 0 (32-byte x-only keys) or 1 (64-byte objects)")
+        if msglen < 0:
+            raise ValueError("schnorrsig_verify_all: msglen must not be negative")
+        if sigs is None or msgs is None or pubkeys is None:
+            raise ValueError("schnorrsig_verify_all: missing array")
+        sigs = _u8(sigs); msgs = _u8(msgs); pubkeys = _u8(pubkeys); n = sigs.size // 64
+        _need("schnorrsig_verify_all sigs", sigs, 64 * n); _need("schnorrsig_verify_all msgs", msgs, msglen * n)
+        _need("schnorrsig_verify_all pubkeys", pubkeys, (64 if pk_format else 32) * n)
+        verdict = np.zeros(1, np.int32); res = np.zeros(max(n, 1), np.int32) if locate else None; seed = np.zeros(32, np.uint8) if want_seed else None
+        self._check(self._lib.secp256k1_schnorrsig_verify_all(self._h, _p(verdict), _p(res), _p(seed), _p(sigs) if n else None, _p(msgs) if msgs.size else None, msglen,
+                                                              _p(pubkeys) if n else None, pk_format, n), "secp256k1_schnorrsig_verify_all")
+        out = (int(verdict[0]),) + ((res[:n],) if locate else ()) + ((seed.tobytes(),) if want_seed else ())
+        return out[0] if len(out) == 1 else out
+
+    def schnorrsig_verify_all_dev(self, verdict, sigs, msgs, pubkeys, msglen=32, pk_format=0, seed_out=None, n=None, stream=None):
+        """every array in HBM (torch tensors): verdict int32[1], seed_out uint8[32] or None; nothing is read back"""
+        if pk_format not in (0, 1):
+            raise ValueError("schnorrsig_verify_all_dev: pk_format must be 0 or 1")
+        if n is None:
+            n = sigs.numel() // 64
+        if verdict is None or verdict.numel() < 1 or (seed_out is not None and seed_out.numel() < 32):
+            raise ValueError("schnorrsig_verify_all_dev: verdict needs one int32 and seed_out 32 bytes")
+        if n and (sigs.numel() < 64 * n or pubkeys.numel() < (64 if pk_format else 32) * n or (msglen and msgs.numel() < msglen * n)):
+            raise ValueError("schnorrsig_verify_all_dev: fewer signature / message / key bytes than n needs")
+        self._check(self._lib.secp256k1_schnorrsig_verify_all_dev(self._h, stream, _dp(verdict), _dp(seed_out), _dp(sigs) if n else None, _dp(msgs) if n and msglen else None,
+                                                                  msglen, _dp(pubkeys) if n else None, pk_format, n), "secp256k1_schnorrsig_verify_all_dev")
+
+    def schnorr_all_last_split_ms(self):
+        """[lift + item hashes, tree + seed, coefficients + scalar sum, MSM] of the most recent verify_all call, in ms (after sync())"""
+        out = np.full(4, -1.0, np.float32)
+        self._check(self._lib.s2k_schnorr_all_last_split_ms(self._h, _p(out)), "s2k_schnorr_all_last_split_ms")
+        return [float(x) for x in out]
+
     # ---- secp256k1_ecdsa_verify (secp256k1.c:498-512, ecdsa_impl.h:195-272) and secp256k1_ecdsa_recover (modules/recovery/main_impl.h:87-157), batched ----
     def ecdsa_verify_batch(self, sigs, msghashes, pubkeys, sig_format=0, pk_format=0):
         """sig_format 0: n*64 compact, 1: n*64 secp256k1_ecdsa_signature objects, 2: DER -- a list of bytes (packed here) or the tuple (data, offsets[n+1]);
