@@ -784,6 +784,49 @@ S2K_API int secp256k1_bppp_norm_product_verify_batch(s2k_engine* e, int32_t* res
                                                      size_t n_gens, size_t g_len, const unsigned char* c_vec, size_t c_vec_len,
                                                      const unsigned char* commits33, size_t n);
 
+/* ---- Bulletproofs++ norm arguments: one verdict for a whole batch over ONE generator set, as a single multi-scalar multiplication ----
+ * *verdict = AND over p of secp256k1_bppp_rangeproof_norm_product_verify(ctx, scratch, proof_p, proof_len, &transcript_p, &rho_p,
+ *                                       g_vec, g_len, c_vec_p, c_vec_len, &commit_p)      (src/modules/bppp/bppp_norm_product_impl.h:425-552)
+ * The reference verifies one proof per call (a `static`); this is how Bulletproofs are verified in bulk.  With sc[p][t] the scalars the
+ * per-item verifier multiplies proof p's terms by (generators, G, -1 for the commitment, -gamma_i and -(gamma_i^2 - 1) for X_i and R_i)
+ * and D_p = sum_t sc[p][t] P_{p,t} the sum it requires to be infinity, the call checks  sum_p z'_p D_p == infinity  as ONE sum:
+ *   generator t:  S_t = sum_p z'_p sc[p][t] mod n   (n_gens terms for the whole batch)       G:  sum_p z'_p v_p
+ *   per proof:    the commitment with -z'_p, X_{p,i} with -z'_p gamma_{p,i}, R_{p,i} with -z'_p (gamma_{p,i}^2 - 1)     (2 n_rounds + 1 terms)
+ * The verdict is 0 for a shape the reference refuses (:446-461); 0 whenever for ANY proof n or l overflows, rho is 0, or a generator,
+ * the commitment or an X / R does not parse; otherwise 1 exactly when the sum is infinity.  A batch of valid proofs is never refused;
+ * a batch holding an invalid one is accepted with probability at most 2^-128 over the hash that gives the coefficients:
+ *   T(tag, x) = SHA256(SHA256(tag) | SHA256(tag) | x)
+ *   gd   = T("S2K/bppp_all/gens", le64(n_gens) | le64(g_len) | gens33)
+ *   d_p  = T("S2K/bppp_all/item", proof_p | transcript104_p | rho_p | c_vec_p | commit33_p)
+ *   node j of the next level = T("S2K/bppp_all/node", nodes 16j .. min(16j+16, count)-1 of this level), from d_0 .. d_{n-1} until one is left
+ *   seed = T("S2K/bppp_all/seed", le64(n) | le64(proof_len) | le64(c_vec_len) | gd | root)                   (n = 1: root = d_0)
+ *   z_0 = 1;  z_p = the first 16 bytes, big-endian, of T("S2K/bppp_all/rand", seed | le64(p)), 0 replaced by 1
+ *   z'_p = mu z_p mod n,  mu = SHA256("S2K/bppp_all/scale") mod n   (one public factor on every scalar: the statement is unchanged)
+ * All 104 bytes of a transcript object are hashed as given: the bytes of its buffer beyond the fill level change the seed and never
+ * the verdict.  seed32_out (or NULL) receives the seed.
+ *
+ * Arrays as in secp256k1_bppp_norm_product_verify_batch.  The return value is the call's success, the verdict goes to *verdict.  A NULL
+ * array with n > 0 or a NULL verdict is S2K_STATUS_ILLEGAL_ARGUMENT (return 0), and so is a batch of more terms than one sum indexes
+ * (n_gens + n (2 n_rounds + 1) above the limit of s2k_ecmult_multi, or S2K_OPT_MSM_MAX_TERMS: "batch too large"); g_len above 256 is
+ * the engine-level failure of the per-item call.  n == 0 returns 1 with verdict 1 and 32 zero bytes as the seed; a refused shape
+ * leaves 32 zero bytes as well.
+ * results (n entries, or NULL), host form only: when the verdict is 0 the per-item verifier runs on the buffers already uploaded and
+ * results[] says which proofs failed; when it is 1 results[] is all ones.
+ * The _dev form: every array in HBM (gens33_host: the set once more on the host, hashed into gd there), stream-ordered, never
+ * synchronises and writes only verdict_dev[0] and, if asked for, the 32 seed bytes.  It neither needs nor builds the set's fixed-base table.
+ * s2k_bppp_all_last_split_ms: the phases of the engine's most recent call, in ms, valid once its work is complete -- out4[0] the
+ * per-proof scalars and item digests, [1] hash tree, seed and z', [2] column sums and the proofs' own terms, [3] the multi-scalar
+ * multiplication; -1 where there is nothing to report.
+ * Out of scope: group forms, the hook into the reference (it has no such call), several generator sets per call. */
+S2K_API int secp256k1_bppp_norm_product_verify_all(s2k_engine* e, int32_t* verdict, int32_t* results, unsigned char* seed32_out, const unsigned char* proofs,
+                                                   size_t proof_len, const unsigned char* transcripts, const unsigned char* rho, const unsigned char* gens33,
+                                                   size_t n_gens, size_t g_len, const unsigned char* c_vec, size_t c_vec_len, const unsigned char* commits33, size_t n);
+S2K_API int secp256k1_bppp_norm_product_verify_all_dev(s2k_engine* e, void* stream, int32_t* verdict_dev, unsigned char* seed32_out_dev, const unsigned char* proofs,
+                                                       size_t proof_len, const unsigned char* transcripts, const unsigned char* rho, const unsigned char* gens33_dev,
+                                                       const unsigned char* gens33_host, size_t n_gens, size_t g_len, const unsigned char* c_vec, size_t c_vec_len,
+                                                       const unsigned char* commits33, size_t n);
+S2K_API int s2k_bppp_all_last_split_ms(s2k_engine* e, float* out4);
+
 /* ---- `_dev` forms of the calls above (every array in HBM of the engine's GPU, stream-ordered, nothing read back) ------------------
  * Same arguments and per-item results as the host forms.  Where a call needs a few bytes on the host to plan its launches, that is
  * an explicit extra argument: gens33_host (the BP++ generator set, cache key of its fixed-base table), tally_off_host / n_pos_host

@@ -47,6 +47,9 @@ SIGNATURES = {
     "secp256k1_schnorrsig_verify_all": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _c.c_int, _sz]),
     "secp256k1_schnorrsig_verify_all_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _c.c_int, _sz]),
     "s2k_schnorr_all_last_split_ms": (_c.c_int, [_vp, _vp]),
+    "secp256k1_bppp_norm_product_verify_all": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz]),
+    "secp256k1_bppp_norm_product_verify_all_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _sz]),
+    "s2k_bppp_all_last_split_ms": (_c.c_int, [_vp, _vp]),
     "secp256k1_ecdsa_verify_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_verify_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_ecdsa_recover_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz]),

@@ -1031,6 +1031,57 @@ class Engine:
                     "secp256k1_bppp_norm_product_verify_batch")
         return res
 
+    # ---- one verdict for a whole batch of norm arguments over one generator set, as a single multi-scalar multiplication (csrc/bppp_all.h) ----
+    def bppp_norm_product_verify_all(self, proofs, transcripts, rho, gens33, g_len, c_vec, commits33, locate=False, want_seed=False):
+        """1 exactly when every proof of the batch verifies (arguments as bppp_norm_product_verify_batch).  Returns the verdict; with locate=True
+        (verdict, results) where results are the per-proof verdicts (all ones when the verdict is 1); with want_seed=True the 32-byte seed of
+        the coefficients is appended."""
+        what = "bppp_norm_product_verify_all"
+        if proofs is None or transcripts is None or rho is None or gens33 is None or c_vec is None or commits33 is None:
+            raise ValueError(what + ": missing array")
+        if g_len < 0:
+            raise ValueError(what + ": g_len must not be negative")
+        proofs = _u8(proofs); transcripts = _u8(transcripts); rho = _u8(rho); gens33 = _u8(gens33); c_vec = _u8(c_vec); commits33 = _u8(commits33)
+        n = rho.size // 32; n_gens = gens33.size // 33
+        proof_len = proofs.size // max(n, 1); c_len = c_vec.size // 32 // max(n, 1)
+        _need(what + " rho", rho, 32 * n); _need(what + " proofs", proofs, proof_len * n); _need(what + " transcripts", transcripts, 104 * n)
+        _need(what + " c_vec", c_vec, 32 * c_len * n); _need(what + " commits33", commits33, 33 * n); _need(what + " gens33", gens33, 33 * n_gens)
+        if n and (proof_len == 0 or c_len == 0 or n_gens == 0):
+            raise ValueError(what + ": empty proofs, c_vec or generator set")
+        verdict = np.zeros(1, np.int32); res = np.zeros(max(n, 1), np.int32) if locate else None; seed = np.zeros(32, np.uint8) if want_seed else None
+        nz = lambda a: _p(a) if n else None
+        self._check(self._lib.secp256k1_bppp_norm_product_verify_all(self._h, _p(verdict), _p(res), _p(seed), nz(proofs), proof_len, nz(transcripts), nz(rho), nz(gens33),
+                                                                     n_gens, g_len, nz(c_vec), c_len, nz(commits33), n), "secp256k1_" + what)
+        out = (int(verdict[0]),) + ((res[:n],) if locate else ()) + ((seed.tobytes(),) if want_seed else ())
+        return out[0] if len(out) == 1 else out
+
+    def bppp_norm_product_verify_all_dev(self, verdict, proofs, proof_len, transcripts, rho, gens33_dev, gens33_host, g_len, c_vec, c_vec_len, commits33, n,
+                                         seed_out=None, stream=None):
+        """every array in HBM (torch tensors): verdict int32[1], seed_out uint8[32] or None; gens33_host: the same generator set as a numpy array
+        (it is hashed on the host); nothing is read back"""
+        what = "bppp_norm_product_verify_all_dev"
+        if verdict is None or verdict.numel() < 1 or (seed_out is not None and seed_out.numel() < 32):
+            raise ValueError(what + ": verdict needs one int32 and seed_out 32 bytes")
+        if n < 0 or proof_len < 0 or c_vec_len < 0 or g_len < 0:
+            raise ValueError(what + ": negative size")
+        gh = _u8(gens33_host) if gens33_host is not None else None
+        if n:
+            if gh is None or gh.size % 33 or gens33_dev is None or gens33_dev.numel() < gh.size:
+                raise ValueError(what + ": the generator set is needed on the host and on the device, 33 bytes per generator")
+            if (proofs is None or transcripts is None or rho is None or c_vec is None or commits33 is None or proofs.numel() < proof_len * n or transcripts.numel() < 104 * n
+                    or rho.numel() < 32 * n or c_vec.numel() < 32 * c_vec_len * n or commits33.numel() < 33 * n):
+                raise ValueError(what + ": fewer proof / transcript / rho / c_vec / commitment bytes than n needs")
+        nz = lambda t: _dp(t) if n else None
+        self._check(self._lib.secp256k1_bppp_norm_product_verify_all_dev(self._h, stream, _dp(verdict), _dp(seed_out), nz(proofs), proof_len, nz(transcripts), nz(rho),
+                                                                         nz(gens33_dev), _p(gh) if n else None, gh.size // 33 if gh is not None else 0, g_len, nz(c_vec),
+                                                                         c_vec_len, nz(commits33), n), "secp256k1_" + what)
+
+    def bppp_all_last_split_ms(self):
+        """[per-proof scalars + item digests, tree + seed + z', column sums + own terms, MSM] of the most recent verify_all call, in ms (after sync())"""
+        out = np.full(4, -1.0, np.float32)
+        self._check(self._lib.s2k_bppp_all_last_split_ms(self._h, _p(out)), "s2k_bppp_all_last_split_ms")
+        return [float(x) for x in out]
+
 
 class Group:
     """The GPUs of one node behind one handle (s2k_group, include/secp256k1_zkp_amd.h): one engine and one host thread per entry of

@@ -118,7 +118,7 @@ static int bp_ensure_table(s2k_engine* e, hipStream_t st, const u32* gens18, con
     }
     return 1;
 }
-static size_t bpv_ws_bytes(size_t n, const bp_shape& sh) {
+size_t bpv_ws_bytes(size_t n, const bp_shape& sh) {
     const size_t T = sh.n_terms, nt = n * T;
     return ws_need({(size_t)sh.n_gens * 18 * 4, 64, nt * 8 * 4, 4 * n, nt * 28 * 4, nt + 64, (n * (T / 1024 + 1) + 64) * 28 * 4, (n * (T / 1024 + 1) + 64) * 28 * 4, n * 8 * BP_MAX_LOG_G * 4});
 }

@@ -441,7 +441,7 @@ extern "C" s2k_engine* s2k_engine_create(int device) {
     e->stream_pre = nullptr; e->ev_rp_in = nullptr; e->rp_mem_bytes = 0; e->rp_seq = 0; e->rp_inputs_ready = 0;
     e->rp_last_plan[0] = e->rp_last_plan[1] = nullptr;
     e->ha_pin = nullptr; e->ha_pin_words = 0; e->retired_bytes = 0;
-    for (int i = 0; i < 4; i++) e->ev_sa[i] = nullptr;
+    for (int i = 0; i < 4; i++) e->ev_sa[i] = e->ev_ba[i] = nullptr;
     for (int i = 0; i < RP_GEN_SLOTS; i++) e->ev_gen_read[i] = nullptr;
     for (int i = 0; i < 2; i++) { auto& m = e->msm_slot[i]; m.s = m.s2 = nullptr; m.fork = m.join = m.done = m.in = nullptr; m.ws = nullptr; m.ws_bytes = 0; m.seen_epoch = 0; }
     e->msm_seq = 0; e->cur_pipe = 0; e->ev_last_np = nullptr; e->np_epoch = 0; e->np_valid = 0;
@@ -550,6 +550,7 @@ extern "C" void s2k_engine_destroy(s2k_engine* e) {
     if (e->ev_mbox) hipEventDestroy(e->ev_mbox);
     for (int i = 0; i < 4; i++) if (e->ev[i]) hipEventDestroy(e->ev[i]);
     for (int i = 0; i < 4; i++) if (e->ev_sa[i]) hipEventDestroy(e->ev_sa[i]);
+    for (int i = 0; i < 4; i++) if (e->ev_ba[i]) hipEventDestroy(e->ev_ba[i]);
     for (int i = 0; i < 2; i++) {
         if (e->rp_mem[i]) hipFree(e->rp_mem[i]);
         if (e->ev_rp_fork[i]) hipEventDestroy(e->ev_rp_fork[i]);

@@ -1,7 +1,7 @@
 // engine_internal.h -- what the translation units of the gfx950 batch-verification engine share (see include/secp256k1_zkp_amd.h):
 // the engine object, the per-device table pool, error plumbing, workspace carving and the host functions one kernel family offers the others.
 //
-// The library is seventeen translation units, one per kernel family, compiled separately (hipcc --offload-arch=gfx950 -O3 -fPIC -c) and linked
+// The library is eighteen translation units, one per kernel family, compiled separately (hipcc --offload-arch=gfx950 -O3 -fPIC -c) and linked
 // into one shared object (see __graft_entry__.build):
 //   engine_core.hip        table construction, the per-device pool and generator-table cache, engine lifecycle / options / groups,
 //                          s2k_ecmult_batch, BIP-340, the single-item `_amd` forms and the `_group` forms of every family
@@ -21,6 +21,7 @@
 //   engine_s2c.hip         ECDSA sign-to-contract checks, anti-exfil host verification and host commitments (s2c.h)
 //   engine_ellswift.hip    ElligatorSwift decoding and encoding of public keys (ellswift.h)
 //   engine_schnorr_all.hip one-verdict batch verification of BIP-340 signatures as a single multi-scalar multiplication (schnorr_all.h)
+//   engine_bppp_all.hip    one-verdict batch verification of BP++ norm arguments over one generator set as a single multi-scalar multiplication (bppp_all.h)
 // The per-lane arithmetic lives in the headers next to these files.  No device function is called across translation units (no -fgpu-rdc):
 // a family that needs another family's kernels calls the HOST function that launches them.
 // There is no CPU implementation behind the entry points: without a HIP device every call fails loudly.
@@ -142,6 +143,7 @@ struct s2k_engine {
     int ellswift_max_attempts; // S2K_OPT_ELLSWIFT_MAX_ATTEMPTS: the bound of the ElligatorSwift encode loop (engine_ellswift.hip; default and maximum 256)
     u32* ha_pin; size_t ha_pin_words;   // pinned: the chain states of the half-aggregate randomizer hash, walked on the host (host_sha256.h)
     hipEvent_t ev_sa[4];       // engine_schnorr_all.hip, created at its first call: [0],[1] phase boundaries of the most recent call, [2],[3] stand-ins (sa_launch)
+    hipEvent_t ev_ba[4];       // engine_bppp_all.hip, likewise (ba_launch)
     // Buffers this engine has outgrown.  Growing a buffer never waits for the device (round 6; it used to be hipDeviceSynchronize() + hipFree
     // under the engine's lock, i.e. a stall for the longest stream of EVERY engine on the GPU): the new buffer is allocated beside the old
     // one, which may still be read by launches in flight and is only handed back when the engine is known to be idle -- at destruction, at
@@ -244,6 +246,9 @@ void gen_cache_collect(s2k_engine* e, hipStream_t st);
 int engine_rp_slots(s2k_engine* e, size_t nw);
 int rp_ptrs_check(const char* who, int32_t* results, uint64_t* min_value, uint64_t* max_value, const void* const* commit_objs, const unsigned char* const* proofs,
                   const size_t* plens, const unsigned char* const* extra, const size_t* elens, const void* const* gen_objs, size_t n);
+// ---- Bulletproofs++ family (engine_bppp.hip) ----------------------------------------------------------------------------------------------
+// workspace of one launch group of the per-item norm-argument verifier (n proofs of one shape), carved from offset 0
+size_t bpv_ws_bytes(size_t n, const bp_shape& sh);
 // ---- multi-scalar multiplication family (engine_msm.hip) ----------------------------------------------------------------------------------
 // side: where the gated exact path runs (with its fork / join events); arena: which MSM_DIRECT_LANES-sized region of the engine's table
 // arena its lanes use (0: the engine's own calls; 1, 2: the two pipelined slots)
