@@ -1,4 +1,7 @@
-#include "engine_internal.h"
+#include "engine_lanes.h"
+#include "s2c.h"         // the per-format item sizes the `_group` forms split by: ecdsa.h, tweak.h (both through s2c.h), s2c.h, ellswift.h, musig.h
+#include "ellswift.h"
+#include "musig.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // error plumbing
@@ -649,23 +652,10 @@ extern "C" int s2k_ecmult_batch_dev(s2k_engine* e, void* stream, unsigned char* 
                                     const unsigned char* a_inf, const unsigned char* na, const unsigned char* ng, size_t n) {
     if (!e) return s2k_fail("s2k_ecmult_batch_dev", "null engine");
     if (n == 0) return 1;
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    if (!engine_ptab(e, ((std::min(n, e->max_lanes) + 255) / 256) * 256)) return 0;
-    ENGINE_GTAB(e, st);
-    HIPCHK(hipEventRecord(e->ev[0], st));
-    HIPCHK(hipEventRecord(e->ev[2], st));
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);
-        hipLaunchKernelGGL(k_ecmult_batch, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, r_xy + 64 * i0, r_inf + i0, a_xy + 64 * i0,
-                           a_inf ? a_inf + i0 : nullptr, na + 32 * i0, ng ? ng + 32 * i0 : nullptr, e->gtab, e->ptab, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st));
-    HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    return lanes_run(e, stream, n, {true, true, 0}, {}, [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32*) {
+        hipLaunchKernelGGL(k_ecmult_batch, grid, dim3(256), 0, st, r_xy + 64 * i0, r_inf + i0, a_xy + 64 * i0, a_inf ? a_inf + i0 : nullptr, na + 32 * i0,
+                           ng ? ng + 32 * i0 : nullptr, e->gtab, e->ptab, m);
+    });
 }
 extern "C" int s2k_ecmult_batch(s2k_engine* e, unsigned char* r_xy, int32_t* r_inf, const unsigned char* a_xy,
                                 const unsigned char* a_inf, const unsigned char* na, const unsigned char* ng, size_t n) {
@@ -673,20 +663,9 @@ extern "C" int s2k_ecmult_batch(s2k_engine* e, unsigned char* r_xy, int32_t* r_i
     if (n == 0) return 1;
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    if (!engine_workspace(e, ws_need({64 * n, 4 * n, 64 * n, n, 32 * n, 32 * n}))) return 0;
-    ws_carver w{e->ws, 0};
-    unsigned char* d_r = w.take<unsigned char>(64 * n); int32_t* d_inf = w.take<int32_t>(n);
-    unsigned char* d_a = w.take<unsigned char>(64 * n); unsigned char* d_ai = w.take<unsigned char>(n);
-    unsigned char* d_na = w.take<unsigned char>(32 * n); unsigned char* d_ng = w.take<unsigned char>(32 * n);
-    HIPCHK(hipMemcpyAsync(d_a, a_xy, 64 * n, hipMemcpyHostToDevice, e->stream));
-    if (a_inf) HIPCHK(hipMemcpyAsync(d_ai, a_inf, n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_na, na, 32 * n, hipMemcpyHostToDevice, e->stream));
-    if (ng) HIPCHK(hipMemcpyAsync(d_ng, ng, 32 * n, hipMemcpyHostToDevice, e->stream));
-    if (!s2k_ecmult_batch_dev(e, nullptr, d_r, d_inf, d_a, a_inf ? d_ai : nullptr, d_na, ng ? d_ng : nullptr, n)) return 0;
-    HIPCHK(hipMemcpyAsync(r_xy, d_r, 64 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(r_inf, d_inf, 4 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, r_xy, 64 * n}, {nullptr, r_inf, 4 * n}, {a_xy, nullptr, 64 * n}, {a_inf, nullptr, n}, {na, nullptr, 32 * n}, {ng, nullptr, 32 * n}};
+    if (!stage_open(e, b)) return 0;
+    return stage_close(e, b, s2k_ecmult_batch_dev(e, nullptr, b[0].at(), b[1].at<int32_t>(), b[2].at(), b[3].opt(), b[4].at(), b[5].opt(), n));
 }
 
 
@@ -708,22 +687,12 @@ extern "C" int secp256k1_schnorrsig_verify_batch_dev(s2k_engine* e, void* stream
                                                      const unsigned char* msgs, size_t msglen, const unsigned char* pubkeys, int pk_format, size_t n) {
     if (!e) return s2k_fail("secp256k1_schnorrsig_verify_batch_dev", "null engine");
     if (n == 0) return 1;
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    if (!engine_ptab(e, ((std::min(n, e->max_lanes) + 255) / 256) * 256)) return 0;
-    ENGINE_GTAB(e, st);
-    HIPCHK(hipMemsetAsync(results, 0, sizeof(int32_t) * n, st));          // a batch that does not complete never shows an item as valid
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);
-        hipLaunchKernelGGL(k_schnorr_verify, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, results + i0, e->bip340, sigs + 64 * i0, msgs + msglen * i0, msglen,
-                           pubkeys + (pk_format ? 64 : 32) * i0, pk_format, e->gtab, e->ptab, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    const size_t pkb = pk_format ? 64 : 32;
+    return lanes_run(e, stream, n, {true, true, 0}, {{results, sizeof(int32_t) * n}},         // a batch that does not complete never shows an item as valid
+                     [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32*) {
+        hipLaunchKernelGGL(k_schnorr_verify, grid, dim3(256), 0, st, results + i0, e->bip340, sigs + 64 * i0, msgs + msglen * i0, msglen, pubkeys + pkb * i0, pk_format,
+                           e->gtab, e->ptab, m);
+    });
 }
 extern "C" int secp256k1_schnorrsig_verify_batch(s2k_engine* e, int32_t* results, const unsigned char* sigs, const unsigned char* msgs,
                                                  size_t msglen, const unsigned char* pubkeys, int pk_format, size_t n) {
@@ -733,17 +702,9 @@ extern "C" int secp256k1_schnorrsig_verify_batch(s2k_engine* e, int32_t* results
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     const size_t pkb = pk_format ? 64 : 32;
-    if (!engine_workspace(e, ws_need({4 * n, 64 * n, msglen * n + 64, pkb * n}))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n); unsigned char* d_sig = w.take<unsigned char>(64 * n);
-    unsigned char* d_msg = w.take<unsigned char>(msglen * n + 64); unsigned char* d_pk = w.take<unsigned char>(pkb * n);
-    HIPCHK(hipMemcpyAsync(d_sig, sigs, 64 * n, hipMemcpyHostToDevice, e->stream));
-    if (msglen) HIPCHK(hipMemcpyAsync(d_msg, msgs, msglen * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_pk, pubkeys, pkb * n, hipMemcpyHostToDevice, e->stream));
-    if (!secp256k1_schnorrsig_verify_batch_dev(e, nullptr, d_res, d_sig, d_msg, msglen, d_pk, pk_format, n)) return 0;
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n}, {sigs, nullptr, 64 * n}, {msgs, nullptr, msglen * n, 64}, {pubkeys, nullptr, pkb * n}};
+    if (!stage_open(e, b)) return 0;
+    return stage_close(e, b, secp256k1_schnorrsig_verify_batch_dev(e, nullptr, b[0].at<int32_t>(), b[1].at(), b[2].at(), msglen, b[3].at(), pk_format, n));
 }
 
 static s2k_engine* g_default_engine = nullptr;
@@ -1236,6 +1197,24 @@ extern "C" s2k_engine* s2k_group_engine(s2k_group* g, int i) { return (g && i >=
 // share i of n items over k engines: [lo, hi)
 static inline void group_share(size_t n, size_t k, size_t i, size_t& lo, size_t& hi) { lo = n * i / k; hi = n * (i + 1) / k; }
 
+// REPLICA work: takes the group's call lock, zeroes `outs`, runs per_engine(e, lo, hi) for every engine's non-empty share [lo, hi) of the
+// n items, all concurrently, and zeroes `outs` again when an engine fails (an engine failure never leaves part of a batch marked valid)
+template <class PerEngine>
+static int group_by_items(s2k_group* g, size_t n, std::initializer_list<zero_span> outs, PerEngine per_engine) {
+    std::lock_guard<std::mutex> call(g->call_mu);
+    for (const zero_span& z : outs) memset(z.p, 0, z.bytes);
+    const size_t k = g->eng.size();
+    std::vector<std::function<int()>> jobs(k);
+    for (size_t i = 0; i < k; i++) {
+        size_t lo, hi; group_share(n, k, i, lo, hi);
+        s2k_engine* e = g->eng[i];
+        jobs[i] = [=]() -> int { return hi == lo ? 1 : per_engine(e, lo, hi); };
+    }
+    const int ok = group_run(g, jobs);
+    if (!ok) for (const zero_span& z : outs) memset(z.p, 0, z.bytes);
+    return ok;
+}
+
 extern "C" int secp256k1_rangeproof_verify_batch_group(s2k_group* g, int32_t* results, uint64_t* min_value, uint64_t* max_value, const unsigned char* commits33,
                                                        const unsigned char* proofs, const uint64_t* proof_off, const unsigned char* extra, const uint64_t* extra_off,
                                                        const unsigned char* gens64, size_t n) {
@@ -1243,27 +1222,15 @@ extern "C" int secp256k1_rangeproof_verify_batch_group(s2k_group* g, int32_t* re
     if (!g || g->eng.empty()) return s2k_fail(who, "null group");
     if (n == 0) return 1;
     if (!results || !min_value || !max_value || !commits33 || !proofs || !proof_off || !gens64) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
-    std::lock_guard<std::mutex> call(g->call_mu);
-    memset(results, 0, sizeof(int32_t) * n);
-    const size_t k = g->eng.size();
-    std::vector<std::function<int()>> jobs(k);
-    for (size_t i = 0; i < k; i++) {
-        size_t lo, hi; group_share(n, k, i, lo, hi);
-        s2k_engine* e = g->eng[i];
-        jobs[i] = [=]() -> int {
-            if (hi == lo) return 1;
-            const size_t m = hi - lo;
-            std::vector<uint64_t> po(m + 1), eo;
-            for (size_t t = 0; t <= m; t++) po[t] = proof_off[lo + t] - proof_off[lo];
-            const int has_extra = extra && extra_off;
-            if (has_extra) { eo.resize(m + 1); for (size_t t = 0; t <= m; t++) eo[t] = extra_off[lo + t] - extra_off[lo]; }
-            return secp256k1_rangeproof_verify_batch(e, results + lo, min_value + lo, max_value + lo, commits33 + 33 * lo, proofs + proof_off[lo], po.data(),
-                                                     has_extra ? extra + extra_off[lo] : nullptr, has_extra ? eo.data() : nullptr, gens64 + 64 * lo, m);
-        };
-    }
-    const int ok = group_run(g, jobs);
-    if (!ok) memset(results, 0, sizeof(int32_t) * n);                  // an engine failure never leaves part of a batch marked valid
-    return ok;
+    return group_by_items(g, n, {{results, sizeof(int32_t) * n}}, [=](s2k_engine* e, size_t lo, size_t hi) {
+        const size_t m = hi - lo;
+        std::vector<uint64_t> po(m + 1), eo;
+        for (size_t t = 0; t <= m; t++) po[t] = proof_off[lo + t] - proof_off[lo];
+        const int has_extra = extra && extra_off;
+        if (has_extra) { eo.resize(m + 1); for (size_t t = 0; t <= m; t++) eo[t] = extra_off[lo + t] - extra_off[lo]; }
+        return secp256k1_rangeproof_verify_batch(e, results + lo, min_value + lo, max_value + lo, commits33 + 33 * lo, proofs + proof_off[lo], po.data(),
+                                                 has_extra ? extra + extra_off[lo] : nullptr, has_extra ? eo.data() : nullptr, gens64 + 64 * lo, m);
+    });
 }
 extern "C" int secp256k1_rangeproof_verify_batch_ptrs_group(s2k_group* g, int32_t* results, uint64_t* min_value, uint64_t* max_value, const void* const* commit_objs,
                                                             const unsigned char* const* proofs, const size_t* plens, const unsigned char* const* extra, const size_t* elens,
@@ -1272,22 +1239,10 @@ extern "C" int secp256k1_rangeproof_verify_batch_ptrs_group(s2k_group* g, int32_
     if (!g || g->eng.empty()) return s2k_fail(who, "null group");
     if (n == 0) return 1;
     if (!rp_ptrs_check(who, results, min_value, max_value, commit_objs, proofs, plens, extra, elens, gen_objs, n)) return 0;
-    std::lock_guard<std::mutex> call(g->call_mu);
-    memset(results, 0, sizeof(int32_t) * n);
-    const size_t k = g->eng.size();
-    std::vector<std::function<int()>> jobs(k);
-    for (size_t i = 0; i < k; i++) {
-        size_t lo, hi; group_share(n, k, i, lo, hi);
-        s2k_engine* e = g->eng[i];
-        jobs[i] = [=]() -> int {
-            if (hi == lo) return 1;
-            return secp256k1_rangeproof_verify_batch_ptrs(e, results + lo, min_value + lo, max_value + lo, commit_objs + lo, proofs + lo, plens + lo, extra ? extra + lo : nullptr,
-                                                          extra ? elens + lo : nullptr, gen_objs + lo, hi - lo);
-        };
-    }
-    const int ok = group_run(g, jobs);
-    if (!ok) memset(results, 0, sizeof(int32_t) * n);
-    return ok;
+    return group_by_items(g, n, {{results, sizeof(int32_t) * n}}, [=](s2k_engine* e, size_t lo, size_t hi) {
+        return secp256k1_rangeproof_verify_batch_ptrs(e, results + lo, min_value + lo, max_value + lo, commit_objs + lo, proofs + lo, plens + lo, extra ? extra + lo : nullptr,
+                                                      extra ? elens + lo : nullptr, gen_objs + lo, hi - lo);
+    });
 }
 extern "C" int secp256k1_schnorrsig_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const unsigned char* msgs, size_t msglen,
                                                        const unsigned char* pubkeys, int pk_format, size_t n) {
@@ -1295,21 +1250,10 @@ extern "C" int secp256k1_schnorrsig_verify_batch_group(s2k_group* g, int32_t* re
     if (!g || g->eng.empty()) return s2k_fail(who, "null group");
     if (n == 0) return 1;
     if (!results || !sigs || (!msgs && msglen) || !pubkeys) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
-    std::lock_guard<std::mutex> call(g->call_mu);
-    memset(results, 0, sizeof(int32_t) * n);
-    const size_t k = g->eng.size(), pkb = pk_format ? 64 : 32;
-    std::vector<std::function<int()>> jobs(k);
-    for (size_t i = 0; i < k; i++) {
-        size_t lo, hi; group_share(n, k, i, lo, hi);
-        s2k_engine* e = g->eng[i];
-        jobs[i] = [=]() -> int {
-            if (hi == lo) return 1;
-            return secp256k1_schnorrsig_verify_batch(e, results + lo, sigs + 64 * lo, msgs ? msgs + msglen * lo : nullptr, msglen, pubkeys + pkb * lo, pk_format, hi - lo);
-        };
-    }
-    const int ok = group_run(g, jobs);
-    if (!ok) memset(results, 0, sizeof(int32_t) * n);
-    return ok;
+    const size_t pkb = pk_format ? 64 : 32;
+    return group_by_items(g, n, {{results, sizeof(int32_t) * n}}, [=](s2k_engine* e, size_t lo, size_t hi) {
+        return secp256k1_schnorrsig_verify_batch(e, results + lo, sigs + 64 * lo, msgs ? msgs + msglen * lo : nullptr, msglen, pubkeys + pkb * lo, pk_format, hi - lo);
+    });
 }
 // (DER: every engine gets the whole packed array and its own window of the offsets; the host form uploads only the bytes that window spans)
 extern "C" int secp256k1_ecdsa_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
@@ -1317,25 +1261,14 @@ extern "C" int secp256k1_ecdsa_verify_batch_group(s2k_group* g, int32_t* results
     const char* who = "secp256k1_ecdsa_verify_batch_group";
     if (!g || g->eng.empty()) return s2k_fail(who, "null group");
     if (n == 0) return 1;
-    if (!results || !sigs || !msghash32 || !pubkeys || (sig_format == 2 && !sig_off)) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    if (!results || !sigs || !msghash32 || !pubkeys || (sig_format == ECDSA_SIG_DER && !sig_off)) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     if (sig_format < 0 || sig_format > 2 || pk_format < 0 || pk_format > 2) return s2k_fail_arg(who, "unknown sig_format / pk_format");
-    std::lock_guard<std::mutex> call(g->call_mu);
-    memset(results, 0, sizeof(int32_t) * n);
-    const size_t k = g->eng.size(), pkb = pk_format == 0 ? 33 : pk_format == 1 ? 64 : 65;
-    const int der = sig_format == 2;
-    std::vector<std::function<int()>> jobs(k);
-    for (size_t i = 0; i < k; i++) {
-        size_t lo, hi; group_share(n, k, i, lo, hi);
-        s2k_engine* e = g->eng[i];
-        jobs[i] = [=]() -> int {
-            if (hi == lo) return 1;
-            return secp256k1_ecdsa_verify_batch(e, results + lo, der ? sigs : sigs + 64 * lo, der ? sig_off + lo : nullptr, sig_format, msghash32 + 32 * lo,
-                                                pubkeys + pkb * lo, pk_format, hi - lo);
-        };
-    }
-    const int ok = group_run(g, jobs);
-    if (!ok) memset(results, 0, sizeof(int32_t) * n);
-    return ok;
+    const size_t pkb = ecdsa_pk_bytes(pk_format);
+    const int der = sig_format == ECDSA_SIG_DER;
+    return group_by_items(g, n, {{results, sizeof(int32_t) * n}}, [=](s2k_engine* e, size_t lo, size_t hi) {
+        return secp256k1_ecdsa_verify_batch(e, results + lo, der ? sigs : sigs + 64 * lo, der ? sig_off + lo : nullptr, sig_format, msghash32 + 32 * lo, pubkeys + pkb * lo,
+                                            pk_format, hi - lo);
+    });
 }
 extern "C" int secp256k1_ecdsa_adaptor_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* adaptor_sigs162, const unsigned char* pubkeys,
                                                           const unsigned char* msgs32, const unsigned char* enckeys, int pk_format, size_t n) {
@@ -1344,52 +1277,30 @@ extern "C" int secp256k1_ecdsa_adaptor_verify_batch_group(s2k_group* g, int32_t*
     if (n == 0) return 1;
     if (!results || !adaptor_sigs162 || !pubkeys || !msgs32 || !enckeys) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     if (pk_format < 0 || pk_format > 2) return s2k_fail_arg(who, "pk_format must be 0 (compressed), 1 (object) or 2 (uncompressed / hybrid)");
-    std::lock_guard<std::mutex> call(g->call_mu);
-    memset(results, 0, sizeof(int32_t) * n);
-    const size_t k = g->eng.size(), pkb = pk_format == 0 ? 33 : pk_format == 1 ? 64 : 65;
-    std::vector<std::function<int()>> jobs(k);
-    for (size_t i = 0; i < k; i++) {
-        size_t lo, hi; group_share(n, k, i, lo, hi);
-        s2k_engine* e = g->eng[i];
-        jobs[i] = [=]() -> int {
-            if (hi == lo) return 1;
-            return secp256k1_ecdsa_adaptor_verify_batch(e, results + lo, adaptor_sigs162 + 162 * lo, pubkeys + pkb * lo, msgs32 + 32 * lo, enckeys + pkb * lo, pk_format, hi - lo);
-        };
-    }
-    const int ok = group_run(g, jobs);
-    if (!ok) memset(results, 0, sizeof(int32_t) * n);
-    return ok;
+    const size_t pkb = ecdsa_pk_bytes(pk_format);
+    return group_by_items(g, n, {{results, sizeof(int32_t) * n}}, [=](s2k_engine* e, size_t lo, size_t hi) {
+        return secp256k1_ecdsa_adaptor_verify_batch(e, results + lo, adaptor_sigs162 + 162 * lo, pubkeys + pkb * lo, msgs32 + 32 * lo, enckeys + pkb * lo, pk_format, hi - lo);
+    });
 }
 // (split by item index as the ECDSA form; msghash32 == NULL: the commitment check alone)
 static int s2c_group_form(const char* who, s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format, const unsigned char* msghash32,
                           const unsigned char* pubkeys, int pk_format, const unsigned char* data32, const unsigned char* openings, int opening_format, size_t n) {
     if (sig_format < 0 || sig_format > 2 || pk_format < 0 || pk_format > 2 || opening_format < 0 || opening_format > 1) return s2k_fail_arg(who, "unknown sig_format / pk_format / opening_format");
-    std::lock_guard<std::mutex> call(g->call_mu);
-    memset(results, 0, sizeof(int32_t) * n);
-    const size_t k = g->eng.size(), pkb = pk_format == 0 ? 33 : pk_format == 1 ? 64 : 65, ob = opening_format ? 64 : 33;
-    const int der = sig_format == 2;
-    std::vector<std::function<int()>> jobs(k);
-    for (size_t i = 0; i < k; i++) {
-        size_t lo, hi; group_share(n, k, i, lo, hi);
-        s2k_engine* e = g->eng[i];
-        jobs[i] = [=]() -> int {
-            if (hi == lo) return 1;
-            if (!msghash32) return secp256k1_ecdsa_s2c_verify_commit_batch(e, results + lo, der ? sigs : sigs + 64 * lo, der ? sig_off + lo : nullptr, sig_format, data32 + 32 * lo,
-                                                                           openings + ob * lo, opening_format, hi - lo);
-            return secp256k1_anti_exfil_host_verify_batch(e, results + lo, der ? sigs : sigs + 64 * lo, der ? sig_off + lo : nullptr, sig_format, msghash32 + 32 * lo,
-                                                          pubkeys + pkb * lo, pk_format, data32 + 32 * lo, openings + ob * lo, opening_format, hi - lo);
-        };
-    }
-    const int ok = group_run(g, jobs);
-    if (!ok) memset(results, 0, sizeof(int32_t) * n);
-    return ok;
+    const size_t pkb = ecdsa_pk_bytes(pk_format), ob = s2c_opening_bytes(opening_format);
+    const int der = sig_format == ECDSA_SIG_DER;
+    return group_by_items(g, n, {{results, sizeof(int32_t) * n}}, [=](s2k_engine* e, size_t lo, size_t hi) {
+        if (!msghash32) return secp256k1_ecdsa_s2c_verify_commit_batch(e, results + lo, der ? sigs : sigs + 64 * lo, der ? sig_off + lo : nullptr, sig_format, data32 + 32 * lo,
+                                                                       openings + ob * lo, opening_format, hi - lo);
+        return secp256k1_anti_exfil_host_verify_batch(e, results + lo, der ? sigs : sigs + 64 * lo, der ? sig_off + lo : nullptr, sig_format, msghash32 + 32 * lo,
+                                                      pubkeys + pkb * lo, pk_format, data32 + 32 * lo, openings + ob * lo, opening_format, hi - lo);
+    });
 }
 extern "C" int secp256k1_ecdsa_s2c_verify_commit_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
                                                              const unsigned char* data32, const unsigned char* openings, int opening_format, size_t n) {
     const char* who = "secp256k1_ecdsa_s2c_verify_commit_batch_group";
     if (!g || g->eng.empty()) return s2k_fail(who, "null group");
     if (n == 0) return 1;
-    if (!results || !sigs || !data32 || !openings || (sig_format == 2 && !sig_off)) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    if (!results || !sigs || !data32 || !openings || (sig_format == ECDSA_SIG_DER && !sig_off)) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     return s2c_group_form(who, g, results, sigs, sig_off, sig_format, nullptr, nullptr, 0, data32, openings, opening_format, n);
 }
 extern "C" int secp256k1_anti_exfil_host_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
@@ -1398,7 +1309,7 @@ extern "C" int secp256k1_anti_exfil_host_verify_batch_group(s2k_group* g, int32_
     const char* who = "secp256k1_anti_exfil_host_verify_batch_group";
     if (!g || g->eng.empty()) return s2k_fail(who, "null group");
     if (n == 0) return 1;
-    if (!results || !sigs || !msghash32 || !pubkeys || !host_data32 || !openings || (sig_format == 2 && !sig_off)) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    if (!results || !sigs || !msghash32 || !pubkeys || !host_data32 || !openings || (sig_format == ECDSA_SIG_DER && !sig_off)) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     return s2c_group_form(who, g, results, sigs, sig_off, sig_format, msghash32, pubkeys, pk_format, host_data32, openings, opening_format, n);
 }
 // (split by item index; every engine decodes its share into its slice of `out`)
@@ -1408,18 +1319,10 @@ extern "C" int secp256k1_ellswift_decode_batch_group(s2k_group* g, unsigned char
     if (n == 0) return 1;
     if (!out || !ell64) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     if (out_format < 0 || out_format > 2) return s2k_fail_arg(who, "out_format must be 0 (n*32 x only), 1 (n*64 objects) or 2 (n*33 compressed)");
-    std::lock_guard<std::mutex> call(g->call_mu);
-    const size_t k = g->eng.size(), ob = out_format == 0 ? 32 : out_format == 1 ? 64 : 33;
-    memset(out, 0, ob * n);
-    std::vector<std::function<int()>> jobs(k);
-    for (size_t i = 0; i < k; i++) {
-        size_t lo, hi; group_share(n, k, i, lo, hi);
-        s2k_engine* e = g->eng[i];
-        jobs[i] = [=]() -> int { return hi == lo ? 1 : secp256k1_ellswift_decode_batch(e, out + ob * lo, out_format, ell64 + 64 * lo, hi - lo); };
-    }
-    const int ok = group_run(g, jobs);
-    if (!ok) memset(out, 0, ob * n);
-    return ok;
+    const size_t ob = ellswift_out_bytes(out_format);
+    return group_by_items(g, n, {{out, ob * n}}, [=](s2k_engine* e, size_t lo, size_t hi) {
+        return secp256k1_ellswift_decode_batch(e, out + ob * lo, out_format, ell64 + 64 * lo, hi - lo);
+    });
 }
 // (the items are shared out; every engine uploads the whole cache and session arrays, and session_of is checked here, once)
 extern "C" int secp256k1_musig_partial_sig_verify_batch_group(s2k_group* g, int32_t* results, const unsigned char* partial_sigs, int sig_format,
@@ -1433,24 +1336,14 @@ extern "C" int secp256k1_musig_partial_sig_verify_batch_group(s2k_group* g, int3
     if (sig_format < 0 || sig_format > 1 || nonce_format < 0 || nonce_format > 1 || pk_format < 0 || pk_format > 2) return s2k_fail_arg(who, "unknown sig_format / nonce_format / pk_format");
     if (n_sessions == 0 || (!session_of && n_sessions != n)) return s2k_fail_arg(who, "n_sessions must be n when session_of is NULL, and never 0");
     if (session_of) for (size_t i = 0; i < n; i++) if (session_of[i] >= n_sessions) return s2k_fail_arg(who, "session_of holds an index >= n_sessions");
-    std::lock_guard<std::mutex> call(g->call_mu);
-    memset(results, 0, sizeof(int32_t) * n);
-    const size_t k = g->eng.size(), sgb = sig_format ? 36 : 32, nb = nonce_format ? 132 : 66, pkb = pk_format == 0 ? 33 : pk_format == 1 ? 64 : 65;
-    std::vector<std::function<int()>> jobs(k);
-    for (size_t i = 0; i < k; i++) {
-        size_t lo, hi; group_share(n, k, i, lo, hi);
-        s2k_engine* e = g->eng[i];
-        jobs[i] = [=]() -> int {
-            if (hi == lo) return 1;
-            if (!session_of) return secp256k1_musig_partial_sig_verify_batch(e, results + lo, partial_sigs + sgb * lo, sig_format, pubnonces + nb * lo, nonce_format, pubkeys + pkb * lo,
-                                                                             pk_format, keyagg_caches197 + 197 * lo, sessions133 + 133 * lo, hi - lo, nullptr, hi - lo);
-            return secp256k1_musig_partial_sig_verify_batch(e, results + lo, partial_sigs + sgb * lo, sig_format, pubnonces + nb * lo, nonce_format, pubkeys + pkb * lo, pk_format,
-                                                            keyagg_caches197, sessions133, n_sessions, session_of + lo, hi - lo);
-        };
-    }
-    const int ok = group_run(g, jobs);
-    if (!ok) memset(results, 0, sizeof(int32_t) * n);
-    return ok;
+    const size_t sgb = musig_sig_bytes(sig_format), nb = musig_nonce_bytes(nonce_format), pkb = ecdsa_pk_bytes(pk_format);
+    return group_by_items(g, n, {{results, sizeof(int32_t) * n}}, [=](s2k_engine* e, size_t lo, size_t hi) {
+        if (!session_of) return secp256k1_musig_partial_sig_verify_batch(e, results + lo, partial_sigs + sgb * lo, sig_format, pubnonces + nb * lo, nonce_format, pubkeys + pkb * lo,
+                                                                         pk_format, keyagg_caches197 + (size_t)MUSIG_CACHE_BYTES * lo, sessions133 + (size_t)MUSIG_SESSION_BYTES * lo,
+                                                                         hi - lo, nullptr, hi - lo);
+        return secp256k1_musig_partial_sig_verify_batch(e, results + lo, partial_sigs + sgb * lo, sig_format, pubnonces + nb * lo, nonce_format, pubkeys + pkb * lo, pk_format,
+                                                        keyagg_caches197, sessions133, n_sessions, session_of + lo, hi - lo);
+    });
 }
 extern "C" int secp256k1_xonly_pubkey_tweak_add_check_batch_group(s2k_group* g, int32_t* results, const unsigned char* tweaked32, const unsigned char* parities,
                                                                   const unsigned char* internal_keys, int key_format, const unsigned char* tweaks32, size_t n) {
@@ -1459,21 +1352,10 @@ extern "C" int secp256k1_xonly_pubkey_tweak_add_check_batch_group(s2k_group* g, 
     if (n == 0) return 1;
     if (!results || !tweaked32 || !parities || !internal_keys || !tweaks32) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     if (key_format < 0 || key_format > 1) return s2k_fail_arg(who, "key_format must be 0 (x-only, 32 bytes) or 1 (object)");
-    std::lock_guard<std::mutex> call(g->call_mu);
-    memset(results, 0, sizeof(int32_t) * n);
-    const size_t k = g->eng.size(), kb = key_format ? 64 : 32;
-    std::vector<std::function<int()>> jobs(k);
-    for (size_t i = 0; i < k; i++) {
-        size_t lo, hi; group_share(n, k, i, lo, hi);
-        s2k_engine* e = g->eng[i];
-        jobs[i] = [=]() -> int {
-            if (hi == lo) return 1;
-            return secp256k1_xonly_pubkey_tweak_add_check_batch(e, results + lo, tweaked32 + 32 * lo, parities + lo, internal_keys + kb * lo, key_format, tweaks32 + 32 * lo, hi - lo);
-        };
-    }
-    const int ok = group_run(g, jobs);
-    if (!ok) memset(results, 0, sizeof(int32_t) * n);
-    return ok;
+    const size_t kb = tweak_key_bytes(key_format);
+    return group_by_items(g, n, {{results, sizeof(int32_t) * n}}, [=](s2k_engine* e, size_t lo, size_t hi) {
+        return secp256k1_xonly_pubkey_tweak_add_check_batch(e, results + lo, tweaked32 + 32 * lo, parities + lo, internal_keys + kb * lo, key_format, tweaks32 + 32 * lo, hi - lo);
+    });
 }
 // One sum over the group.  Per engine i: its slice's scalars / points (device memory of engine i's GPU when `resident`, host memory
 // otherwise); the generator term goes with slice 0.  The result comes back to the host (r_xy 64 bytes, *r_inf).

@@ -1,4 +1,4 @@
-#include "engine_internal.h"
+#include "engine_lanes.h"
 #include "generator.h"
 
 // ------------------------------------------------------------------------------------------------------------
@@ -47,22 +47,10 @@ extern "C" int secp256k1_generator_generate_batch_dev(s2k_engine* e, void* strea
     if (!e) return s2k_fail(who, "null engine");
     if (n == 0) return 1;
     if (!results || !gens_out64 || !keys32) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    ENGINE_GTAB(e, st);
-    HIPCHK(hipMemsetAsync(results, 0, sizeof(int32_t) * n, st));          // a batch that does not complete shows no item as generated
-    HIPCHK(hipMemsetAsync(gens_out64, 0, 64 * n, st));
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);
-        hipLaunchKernelGGL(k_gen_generate, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, results + i0, gens_out64 + 64 * i0, keys32 + 32 * i0,
-                           blinds32 ? blinds32 + 32 * i0 : nullptr, e->gtab, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    return lanes_run(e, stream, n, {true, false, 0}, {{results, sizeof(int32_t) * n}, {gens_out64, 64 * n}},       // a batch that does not complete shows no item as generated
+                     [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32*) {
+        hipLaunchKernelGGL(k_gen_generate, grid, dim3(256), 0, st, results + i0, gens_out64 + 64 * i0, keys32 + 32 * i0, blinds32 ? blinds32 + 32 * i0 : nullptr, e->gtab, m);
+    });
 }
 extern "C" int secp256k1_generator_generate_batch(s2k_engine* e, int32_t* results, unsigned char* gens_out64, const unsigned char* keys32,
                                                   const unsigned char* blinds32, size_t n) {
@@ -73,17 +61,9 @@ extern "C" int secp256k1_generator_generate_batch(s2k_engine* e, int32_t* result
     memset(results, 0, sizeof(int32_t) * n); memset(gens_out64, 0, 64 * n);
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    if (!engine_workspace(e, ws_need({4 * n, 64 * n, 32 * n, 32 * n}))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n); unsigned char* d_gen = w.take<unsigned char>(64 * n); unsigned char* d_key = w.take<unsigned char>(32 * n);
-    unsigned char* d_bl = w.take<unsigned char>(32 * n);
-    HIPCHK(hipMemcpyAsync(d_key, keys32, 32 * n, hipMemcpyHostToDevice, e->stream));
-    if (blinds32) HIPCHK(hipMemcpyAsync(d_bl, blinds32, 32 * n, hipMemcpyHostToDevice, e->stream));
-    if (!secp256k1_generator_generate_batch_dev(e, nullptr, d_res, d_gen, d_key, blinds32 ? d_bl : nullptr, n)) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(gens_out64, d_gen, 64 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n}, {nullptr, gens_out64, 64 * n}, {keys32, nullptr, 32 * n}, {blinds32, nullptr, 32 * n}};
+    if (!stage_open(e, b)) return 0;
+    return stage_close(e, b, secp256k1_generator_generate_batch_dev(e, nullptr, b[0].at<int32_t>(), b[1].at(), b[2].at(), b[3].opt(), n));
 }
 
 // ---- secp256k1_generator_parse ----------------------------------------------------------------------------------------------------
@@ -92,20 +72,10 @@ extern "C" int secp256k1_generator_parse_batch_dev(s2k_engine* e, void* stream, 
     if (!e) return s2k_fail(who, "null engine");
     if (n == 0) return 1;
     if (!results || !gens_out64 || !gens33) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    HIPCHK(hipMemsetAsync(results, 0, sizeof(int32_t) * n, st));          // a batch that does not complete shows no item as parsed
-    HIPCHK(hipMemsetAsync(gens_out64, 0, 64 * n, st));
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);
-        hipLaunchKernelGGL(k_gen_parse, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, results + i0, gens_out64 + 64 * i0, gens33 + 33 * i0, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    return lanes_run(e, stream, n, {false, false, 0}, {{results, sizeof(int32_t) * n}, {gens_out64, 64 * n}},      // a batch that does not complete shows no item as parsed
+                     [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32*) {
+        hipLaunchKernelGGL(k_gen_parse, grid, dim3(256), 0, st, results + i0, gens_out64 + 64 * i0, gens33 + 33 * i0, m);
+    });
 }
 extern "C" int secp256k1_generator_parse_batch(s2k_engine* e, int32_t* results, unsigned char* gens_out64, const unsigned char* gens33, size_t n) {
     const char* who = "secp256k1_generator_parse_batch";
@@ -115,15 +85,9 @@ extern "C" int secp256k1_generator_parse_batch(s2k_engine* e, int32_t* results, 
     memset(results, 0, sizeof(int32_t) * n); memset(gens_out64, 0, 64 * n);
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    if (!engine_workspace(e, ws_need({4 * n, 64 * n, 33 * n}))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n); unsigned char* d_gen = w.take<unsigned char>(64 * n); unsigned char* d_in = w.take<unsigned char>(33 * n);
-    HIPCHK(hipMemcpyAsync(d_in, gens33, 33 * n, hipMemcpyHostToDevice, e->stream));
-    if (!secp256k1_generator_parse_batch_dev(e, nullptr, d_res, d_gen, d_in, n)) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(gens_out64, d_gen, 64 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n}, {nullptr, gens_out64, 64 * n}, {gens33, nullptr, 33 * n}};
+    if (!stage_open(e, b)) return 0;
+    return stage_close(e, b, secp256k1_generator_parse_batch_dev(e, nullptr, b[0].at<int32_t>(), b[1].at(), b[2].at(), n));
 }
 
 // ---- secp256k1_generator_serialize ------------------------------------------------------------------------------------------------
@@ -132,19 +96,9 @@ extern "C" int secp256k1_generator_serialize_batch_dev(s2k_engine* e, void* stre
     if (!e) return s2k_fail(who, "null engine");
     if (n == 0) return 1;
     if (!out33 || !gens64) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    HIPCHK(hipMemsetAsync(out33, 0, 33 * n, st));
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);
-        hipLaunchKernelGGL(k_gen_serialize, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, out33 + 33 * i0, gens64 + 64 * i0, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    return lanes_run(e, stream, n, {false, false, 0}, {{out33, 33 * n}}, [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32*) {
+        hipLaunchKernelGGL(k_gen_serialize, grid, dim3(256), 0, st, out33 + 33 * i0, gens64 + 64 * i0, m);
+    });
 }
 extern "C" int secp256k1_generator_serialize_batch(s2k_engine* e, unsigned char* out33, const unsigned char* gens64, size_t n) {
     const char* who = "secp256k1_generator_serialize_batch";
@@ -154,14 +108,9 @@ extern "C" int secp256k1_generator_serialize_batch(s2k_engine* e, unsigned char*
     memset(out33, 0, 33 * n);
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    if (!engine_workspace(e, ws_need({33 * n, 64 * n}))) return 0;
-    ws_carver w{e->ws, 0};
-    unsigned char* d_out = w.take<unsigned char>(33 * n); unsigned char* d_gen = w.take<unsigned char>(64 * n);
-    HIPCHK(hipMemcpyAsync(d_gen, gens64, 64 * n, hipMemcpyHostToDevice, e->stream));
-    if (!secp256k1_generator_serialize_batch_dev(e, nullptr, d_out, d_gen, n)) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(out33, d_out, 33 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, out33, 33 * n}, {gens64, nullptr, 64 * n}};
+    if (!stage_open(e, b)) return 0;
+    return stage_close(e, b, secp256k1_generator_serialize_batch_dev(e, nullptr, b[0].at(), b[1].at(), n));
 }
 
 // ---- secp256k1_pedersen_commit ----------------------------------------------------------------------------------------------------
@@ -171,23 +120,11 @@ extern "C" int secp256k1_pedersen_commit_batch_dev(s2k_engine* e, void* stream, 
     if (!e) return s2k_fail(who, "null engine");
     if (n == 0) return 1;
     if (!results || !commits_out33 || !values || !gens64) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    if (!engine_ptab(e, ((std::min(n, e->max_lanes) + 255) / 256) * 256)) return 0;
-    ENGINE_GTAB(e, st);
-    HIPCHK(hipMemsetAsync(results, 0, sizeof(int32_t) * n, st));          // a batch that does not complete shows no item as committed
-    HIPCHK(hipMemsetAsync(commits_out33, 0, 33 * n, st));
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);
-        hipLaunchKernelGGL(k_pedersen_commit, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, results + i0, commits_out33 + 33 * i0,
-                           blinds32 ? blinds32 + 32 * i0 : nullptr, values + i0, gens64 + 64 * i0, e->gtab, e->ptab, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    return lanes_run(e, stream, n, {true, true, 0}, {{results, sizeof(int32_t) * n}, {commits_out33, 33 * n}},      // a batch that does not complete shows no item as committed
+                     [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32*) {
+        hipLaunchKernelGGL(k_pedersen_commit, grid, dim3(256), 0, st, results + i0, commits_out33 + 33 * i0, blinds32 ? blinds32 + 32 * i0 : nullptr, values + i0,
+                           gens64 + 64 * i0, e->gtab, e->ptab, m);
+    });
 }
 extern "C" int secp256k1_pedersen_commit_batch(s2k_engine* e, int32_t* results, unsigned char* commits_out33, const unsigned char* blinds32,
                                                const uint64_t* values, const unsigned char* gens64, size_t n) {
@@ -198,16 +135,7 @@ extern "C" int secp256k1_pedersen_commit_batch(s2k_engine* e, int32_t* results, 
     memset(results, 0, sizeof(int32_t) * n); memset(commits_out33, 0, 33 * n);
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    if (!engine_workspace(e, ws_need({4 * n, 33 * n, 32 * n, 8 * n, 64 * n}))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n); unsigned char* d_out = w.take<unsigned char>(33 * n); unsigned char* d_bl = w.take<unsigned char>(32 * n);
-    uint64_t* d_val = w.take<uint64_t>(n); unsigned char* d_gen = w.take<unsigned char>(64 * n);
-    if (blinds32) HIPCHK(hipMemcpyAsync(d_bl, blinds32, 32 * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_val, values, 8 * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_gen, gens64, 64 * n, hipMemcpyHostToDevice, e->stream));
-    if (!secp256k1_pedersen_commit_batch_dev(e, nullptr, d_res, d_out, blinds32 ? d_bl : nullptr, d_val, d_gen, n)) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(commits_out33, d_out, 33 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n}, {nullptr, commits_out33, 33 * n}, {blinds32, nullptr, 32 * n}, {values, nullptr, 8 * n}, {gens64, nullptr, 64 * n}};
+    if (!stage_open(e, b)) return 0;
+    return stage_close(e, b, secp256k1_pedersen_commit_batch_dev(e, nullptr, b[0].at<int32_t>(), b[1].at(), b[2].opt(), b[3].at<uint64_t>(), b[4].at(), n));
 }

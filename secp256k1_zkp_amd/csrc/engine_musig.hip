@@ -1,12 +1,10 @@
-#include "engine_internal.h"
+#include "engine_lanes.h"
 #include "musig.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // MuSig2, the coordinator's half (musig.h): batch partial-signature verification and nonce processing, one item per lane
 // ------------------------------------------------------------------------------------------------------------
-// Both kernels park a point between two stages (musig.h).  The parking area lies behind the per-lane tables in the engine's table
-// buffer, as in engine_adaptor.hip: word k of lane i of a launch of L lanes at park[k * L + i].
-static size_t musig_park_lanes(size_t lanes, size_t words) { return (lanes * words + S2K_PTAB_WORDS - 1) / S2K_PTAB_WORDS; }      // the area, counted in table slices
+// Both kernels park a point between two stages (musig.h), in the parking area behind the per-lane tables (engine_lanes.h: park_lanes).
 
 // (no lane leaves early: ecmult_lane2 votes over the wavefront)
 __global__ void __launch_bounds__(256, 2)
@@ -57,29 +55,16 @@ extern "C" int secp256k1_musig_partial_sig_verify_batch_dev(s2k_engine* e, void*
     if (!results || !partial_sigs || !pubnonces || !pubkeys || !keyagg_caches197 || !sessions133) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     if (!musig_formats_ok(who, sig_format, nonce_format, pk_format)) return 0;
     if (n_sessions == 0 || (!session_of && n_sessions != n)) return s2k_fail_arg(who, "n_sessions must be n when session_of is NULL, and never 0");
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    const size_t lanes = ((std::min(n, e->max_lanes) + 255) / 256) * 256;
-    if (!engine_ptab(e, lanes + musig_park_lanes(lanes, S2K_MUSIG_PARK_WORDS))) return 0;
-    u32* const park = e->ptab + lanes * S2K_PTAB_WORDS;
-    ENGINE_GTAB(e, st);
     musig_midstates mid; musig_tag_midstates(mid);                        // (six compressions on the host: not worth a field of the engine)
-    HIPCHK(hipMemsetAsync(results, 0, sizeof(int32_t) * n, st));          // a batch that does not complete never shows an item as valid
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
     const size_t sgb = musig_sig_bytes(sig_format), nb = musig_nonce_bytes(nonce_format), pkb = ecdsa_pk_bytes(pk_format);
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);                  // (m <= lanes: every launch's park stride fits the area)
+    return lanes_run(e, stream, n, {true, true, S2K_MUSIG_PARK_WORDS}, {{results, sizeof(int32_t) * n}},      // a batch that does not complete never shows an item as valid
+                     [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32* park) {
         // without session_of item i uses pair i: the pair arrays move with the sub-range, and the pairs left are n_sessions - i0
-        hipLaunchKernelGGL(k_musig_partial_verify, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, results + i0, partial_sigs + sgb * i0, sig_format,
-                           pubnonces + nb * i0, nonce_format, pubkeys + pkb * i0, pk_format, session_of ? keyagg_caches197 : keyagg_caches197 + (size_t)MUSIG_CACHE_BYTES * i0,
+        hipLaunchKernelGGL(k_musig_partial_verify, grid, dim3(256), 0, st, results + i0, partial_sigs + sgb * i0, sig_format, pubnonces + nb * i0, nonce_format,
+                           pubkeys + pkb * i0, pk_format, session_of ? keyagg_caches197 : keyagg_caches197 + (size_t)MUSIG_CACHE_BYTES * i0,
                            session_of ? sessions133 : sessions133 + (size_t)MUSIG_SESSION_BYTES * i0, session_of ? n_sessions : n_sessions - i0,
                            session_of ? session_of + i0 : nullptr, mid, e->gtab, e->ptab, park, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    });
 }
 extern "C" int secp256k1_musig_partial_sig_verify_batch(s2k_engine* e, int32_t* results, const unsigned char* partial_sigs, int sig_format, const unsigned char* pubnonces,
                                                         int nonce_format, const unsigned char* pubkeys, int pk_format, const unsigned char* keyagg_caches197,
@@ -96,22 +81,11 @@ extern "C" int secp256k1_musig_partial_sig_verify_batch(s2k_engine* e, int32_t* 
     HIPCHK(hipSetDevice(e->device));
     const size_t sgb = musig_sig_bytes(sig_format), nb = musig_nonce_bytes(nonce_format), pkb = ecdsa_pk_bytes(pk_format);
     const size_t cb = (size_t)MUSIG_CACHE_BYTES * n_sessions, sb = (size_t)MUSIG_SESSION_BYTES * n_sessions;
-    if (!engine_workspace(e, ws_need({4 * n, 4 * n, sgb * n, nb * n, pkb * n, cb, sb}))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n); uint32_t* d_of = w.take<uint32_t>(n); unsigned char* d_sig = w.take<unsigned char>(sgb * n);
-    unsigned char* d_nonce = w.take<unsigned char>(nb * n); unsigned char* d_pk = w.take<unsigned char>(pkb * n);
-    unsigned char* d_cache = w.take<unsigned char>(cb); unsigned char* d_sess = w.take<unsigned char>(sb);
-    if (session_of) HIPCHK(hipMemcpyAsync(d_of, session_of, 4 * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_sig, partial_sigs, sgb * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_nonce, pubnonces, nb * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_pk, pubkeys, pkb * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_cache, keyagg_caches197, cb, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_sess, sessions133, sb, hipMemcpyHostToDevice, e->stream));
-    if (!secp256k1_musig_partial_sig_verify_batch_dev(e, nullptr, d_res, d_sig, sig_format, d_nonce, nonce_format, d_pk, pk_format, d_cache, d_sess, n_sessions,
-                                                      session_of ? d_of : nullptr, n)) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n}, {session_of, nullptr, 4 * n}, {partial_sigs, nullptr, sgb * n}, {pubnonces, nullptr, nb * n}, {pubkeys, nullptr, pkb * n},
+                     {keyagg_caches197, nullptr, cb}, {sessions133, nullptr, sb}};
+    if (!stage_open(e, b)) return 0;
+    return stage_close(e, b, secp256k1_musig_partial_sig_verify_batch_dev(e, nullptr, b[0].at<int32_t>(), b[2].at(), sig_format, b[3].at(), nonce_format, b[4].at(), pk_format,
+                                                                          b[5].at(), b[6].at(), n_sessions, b[1].opt<uint32_t>(), n));
 }
 
 extern "C" int secp256k1_musig_nonce_process_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* sessions_out133, const unsigned char* aggnonces,
@@ -122,32 +96,17 @@ extern "C" int secp256k1_musig_nonce_process_batch_dev(s2k_engine* e, void* stre
     if (n == 0) return 1;
     if (!results || !sessions_out133 || !aggnonces || !msgs32 || !keyagg_caches197) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     if (nonce_format < 0 || nonce_format > 1) return s2k_fail_arg(who, "nonce_format must be 0 (66 bytes serialised) or 1 (132-byte object)");
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    const size_t lanes = ((std::min(n, e->max_lanes) + 255) / 256) * 256;
-    if (!engine_ptab(e, lanes + musig_park_lanes(lanes, S2K_MUSIG_PARK_R1_WORDS))) return 0;
-    u32* const park = e->ptab + lanes * S2K_PTAB_WORDS;
-    ENGINE_GTAB(e, st);
     musig_midstates mid; musig_tag_midstates(mid);
-    HIPCHK(hipMemsetAsync(results, 0, sizeof(int32_t) * n, st));
-    HIPCHK(hipMemsetAsync(sessions_out133, 0, (size_t)MUSIG_SESSION_BYTES * n, st));
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
     const size_t nb = musig_nonce_bytes(nonce_format);
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);
-        const dim3 grid((unsigned)((m + 255) / 256));
+    return lanes_run(e, stream, n, {true, true, S2K_MUSIG_PARK_R1_WORDS}, {{results, sizeof(int32_t) * n}, {sessions_out133, (size_t)MUSIG_SESSION_BYTES * n}},
+                     [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32* park) {
         if (adaptors64)
             hipLaunchKernelGGL(k_musig_nonce_process<1>, grid, dim3(256), 0, st, results + i0, sessions_out133 + (size_t)MUSIG_SESSION_BYTES * i0, aggnonces + nb * i0,
                                nonce_format, msgs32 + 32 * i0, keyagg_caches197 + (size_t)MUSIG_CACHE_BYTES * i0, adaptors64 + 64 * i0, mid, e->gtab, e->ptab, park, m);
         else
             hipLaunchKernelGGL(k_musig_nonce_process<0>, grid, dim3(256), 0, st, results + i0, sessions_out133 + (size_t)MUSIG_SESSION_BYTES * i0, aggnonces + nb * i0,
                                nonce_format, msgs32 + 32 * i0, keyagg_caches197 + (size_t)MUSIG_CACHE_BYTES * i0, (const unsigned char*)nullptr, mid, e->gtab, e->ptab, park, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    });
 }
 extern "C" int secp256k1_musig_nonce_process_batch(s2k_engine* e, int32_t* results, unsigned char* sessions_out133, const unsigned char* aggnonces, int nonce_format,
                                                    const unsigned char* msgs32, const unsigned char* keyagg_caches197, const unsigned char* adaptors64, size_t n) {
@@ -161,17 +120,8 @@ extern "C" int secp256k1_musig_nonce_process_batch(s2k_engine* e, int32_t* resul
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     const size_t nb = musig_nonce_bytes(nonce_format), cb = (size_t)MUSIG_CACHE_BYTES * n, sb = (size_t)MUSIG_SESSION_BYTES * n;
-    if (!engine_workspace(e, ws_need({4 * n, sb, nb * n, 32 * n, cb, 64 * n}))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n); unsigned char* d_out = w.take<unsigned char>(sb); unsigned char* d_nonce = w.take<unsigned char>(nb * n);
-    unsigned char* d_msg = w.take<unsigned char>(32 * n); unsigned char* d_cache = w.take<unsigned char>(cb); unsigned char* d_ad = w.take<unsigned char>(64 * n);
-    HIPCHK(hipMemcpyAsync(d_nonce, aggnonces, nb * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_msg, msgs32, 32 * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_cache, keyagg_caches197, cb, hipMemcpyHostToDevice, e->stream));
-    if (adaptors64) HIPCHK(hipMemcpyAsync(d_ad, adaptors64, 64 * n, hipMemcpyHostToDevice, e->stream));
-    if (!secp256k1_musig_nonce_process_batch_dev(e, nullptr, d_res, d_out, d_nonce, nonce_format, d_msg, d_cache, adaptors64 ? d_ad : nullptr, n)) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(sessions_out133, d_out, sb, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n}, {nullptr, sessions_out133, sb}, {aggnonces, nullptr, nb * n}, {msgs32, nullptr, 32 * n}, {keyagg_caches197, nullptr, cb},
+                     {adaptors64, nullptr, 64 * n}};
+    if (!stage_open(e, b)) return 0;
+    return stage_close(e, b, secp256k1_musig_nonce_process_batch_dev(e, nullptr, b[0].at<int32_t>(), b[1].at(), b[2].at(), nonce_format, b[3].at(), b[4].at(), b[5].opt(), n));
 }

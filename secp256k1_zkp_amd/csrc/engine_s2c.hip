@@ -1,4 +1,4 @@
-#include "engine_internal.h"
+#include "engine_lanes.h"
 #include "s2c.h"
 
 // ------------------------------------------------------------------------------------------------------------
@@ -71,23 +71,14 @@ extern "C" int secp256k1_ecdsa_s2c_verify_commit_batch_dev(s2k_engine* e, void* 
     if (n == 0) return 1;
     if (!results || !sigs || !data32 || !openings || (sig_format == ECDSA_SIG_DER && !sig_off)) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     if (!s2c_formats_ok(who, sig_format, 0, opening_format)) return 0;
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    ENGINE_GTAB(e, st);
     s2c_midstates mid; s2c_tag_midstates(mid);                            // (four compressions on the host: not worth a field of the engine)
-    HIPCHK(hipMemsetAsync(results, 0, sizeof(int32_t) * n, st));          // a batch that does not complete never shows an item as valid
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
+    const int der = sig_format == ECDSA_SIG_DER;
     const size_t ob = s2c_opening_bytes(opening_format);
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);
-        hipLaunchKernelGGL(k_s2c_commit, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, results + i0, sig_format == ECDSA_SIG_DER ? sigs : sigs + 64 * i0,
-                           sig_format == ECDSA_SIG_DER ? sig_off + i0 : nullptr, sig_format, data32 + 32 * i0, openings + ob * i0, opening_format, mid, e->gtab, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    return lanes_run(e, stream, n, {true, false, 0}, {{results, sizeof(int32_t) * n}},        // a batch that does not complete never shows an item as valid
+                     [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32*) {
+        hipLaunchKernelGGL(k_s2c_commit, grid, dim3(256), 0, st, results + i0, der ? sigs : sigs + 64 * i0, der ? sig_off + i0 : nullptr, sig_format, data32 + 32 * i0,
+                           openings + ob * i0, opening_format, mid, e->gtab, m);
+    });
 }
 
 extern "C" int secp256k1_anti_exfil_host_verify_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off,
@@ -98,21 +89,13 @@ extern "C" int secp256k1_anti_exfil_host_verify_batch_dev(s2k_engine* e, void* s
     if (n == 0) return 1;
     if (!results || !sigs || !msghash32 || !pubkeys || !host_data32 || !openings || (sig_format == ECDSA_SIG_DER && !sig_off)) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     if (!s2c_formats_ok(who, sig_format, pk_format, opening_format)) return 0;
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    if (!engine_ptab(e, ((std::min(n, e->max_lanes) + 255) / 256) * 256)) return 0;
-    ENGINE_GTAB(e, st);
     s2c_midstates mid; s2c_tag_midstates(mid);
-    HIPCHK(hipMemsetAsync(results, 0, sizeof(int32_t) * n, st));          // a batch that does not complete never shows an item as valid
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
+    const int der = sig_format == ECDSA_SIG_DER;
     const size_t pkb = ecdsa_pk_bytes(pk_format), ob = s2c_opening_bytes(opening_format);
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);
-        const dim3 grid((unsigned)((m + 255) / 256));
-        const unsigned char* sg = sig_format == ECDSA_SIG_DER ? sigs : sigs + 64 * i0;
-        const uint64_t* so = sig_format == ECDSA_SIG_DER ? sig_off + i0 : nullptr;
+    return lanes_run(e, stream, n, {true, true, 0}, {{results, sizeof(int32_t) * n}},         // a batch that does not complete never shows an item as valid
+                     [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32*) {
+        const unsigned char* sg = der ? sigs : sigs + 64 * i0;
+        const uint64_t* so = der ? sig_off + i0 : nullptr;
         if (e->s2c_fused) {
             hipLaunchKernelGGL(k_s2c_host_verify, grid, dim3(256), 0, st, results + i0, sg, so, sig_format, msghash32 + 32 * i0, pubkeys + pkb * i0, pk_format,
                                host_data32 + 32 * i0, openings + ob * i0, opening_format, mid, e->gtab, e->ptab, m);
@@ -120,10 +103,7 @@ extern "C" int secp256k1_anti_exfil_host_verify_batch_dev(s2k_engine* e, void* s
             hipLaunchKernelGGL(k_s2c_commit, grid, dim3(256), 0, st, results + i0, sg, so, sig_format, host_data32 + 32 * i0, openings + ob * i0, opening_format, mid, e->gtab, m);
             hipLaunchKernelGGL(k_s2c_ecdsa_and, grid, dim3(256), 0, st, results + i0, sg, so, sig_format, msghash32 + 32 * i0, pubkeys + pkb * i0, pk_format, e->gtab, e->ptab, m);
         }
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    });
 }
 
 // host form of both verifiers: msghash32 == NULL selects the commitment check alone (its callers have checked their own arguments)
@@ -132,37 +112,18 @@ static int s2c_host_form(const char* who, s2k_engine* e, int32_t* results, const
                          int opening_format, size_t n) {
     memset(results, 0, sizeof(int32_t) * n);
     if (!s2c_formats_ok(who, sig_format, pk_format, opening_format)) return 0;
-    const int der = sig_format == ECDSA_SIG_DER, full = msghash32 != nullptr;
-    if (der) for (size_t i = 0; i < n; i++) if (sig_off[i + 1] < sig_off[i]) return s2k_fail_arg(who, "sig_off must not decrease");
+    const int full = msghash32 != nullptr;
+    der_span sw;
+    if (!der_window(who, sw, sigs, sig_off, sig_format, n)) return 0;
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    // DER: the items' bytes [sig_off[0], sig_off[n]) go to HBM as they are; the offsets stay the caller's, the base pointer moves back
-    const size_t sig_lo = der ? (size_t)sig_off[0] : 0, sig_bytes = der ? (size_t)(sig_off[n] - sig_off[0]) : 64 * n;
     const size_t pkb = full ? ecdsa_pk_bytes(pk_format) : 0, ob = s2c_opening_bytes(opening_format);
-    if (!engine_workspace(e, ws_need({4 * n, sig_bytes + 64, 8 * (n + 1), 32 * n, pkb * n, 32 * n, ob * n}))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n); unsigned char* d_sig = w.take<unsigned char>(sig_bytes + 64); uint64_t* d_off = w.take<uint64_t>(n + 1);
-    unsigned char* d_msg = w.take<unsigned char>(32 * n); unsigned char* d_pk = w.take<unsigned char>(pkb * n);
-    unsigned char* d_dat = w.take<unsigned char>(32 * n); unsigned char* d_op = w.take<unsigned char>(ob * n);
-    std::vector<uint64_t> rel;
-    if (sig_bytes) HIPCHK(hipMemcpyAsync(d_sig, sigs + sig_lo, sig_bytes, hipMemcpyHostToDevice, e->stream));
-    if (der) {
-        rel.resize(n + 1);
-        for (size_t i = 0; i <= n; i++) rel[i] = sig_off[i] - sig_lo;
-        HIPCHK(hipMemcpyAsync(d_off, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, e->stream));
-    }
-    if (full) {
-        HIPCHK(hipMemcpyAsync(d_msg, msghash32, 32 * n, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipMemcpyAsync(d_pk, pubkeys, pkb * n, hipMemcpyHostToDevice, e->stream));
-    }
-    HIPCHK(hipMemcpyAsync(d_dat, data32, 32 * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_op, openings, ob * n, hipMemcpyHostToDevice, e->stream));
-    const int ok = full ? secp256k1_anti_exfil_host_verify_batch_dev(e, nullptr, d_res, d_sig, der ? d_off : nullptr, sig_format, d_msg, d_pk, pk_format, d_dat, d_op, opening_format, n)
-                        : secp256k1_ecdsa_s2c_verify_commit_batch_dev(e, nullptr, d_res, d_sig, der ? d_off : nullptr, sig_format, d_dat, d_op, opening_format, n);
-    if (!ok) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n}, {sw.lo, nullptr, sw.bytes, 64}, {sw.rel.data(), nullptr, 8 * (n + 1)}, {msghash32, nullptr, 32 * n}, {pubkeys, nullptr, pkb * n},
+                     {data32, nullptr, 32 * n}, {openings, nullptr, ob * n}};
+    if (!stage_open(e, b)) return 0;
+    int32_t* d_res = b[0].at<int32_t>(); const uint64_t* d_off = b[2].opt<uint64_t>();
+    return stage_close(e, b, full ? secp256k1_anti_exfil_host_verify_batch_dev(e, nullptr, d_res, b[1].at(), d_off, sig_format, b[3].at(), b[4].at(), pk_format, b[5].at(), b[6].at(), opening_format, n)
+                                  : secp256k1_ecdsa_s2c_verify_commit_batch_dev(e, nullptr, d_res, b[1].at(), d_off, sig_format, b[5].at(), b[6].at(), opening_format, n));
 }
 extern "C" int secp256k1_ecdsa_s2c_verify_commit_batch(s2k_engine* e, int32_t* results, const unsigned char* sigs, const uint64_t* sig_off, int sig_format,
                                                        const unsigned char* data32, const unsigned char* openings, int opening_format, size_t n) {
@@ -187,20 +148,10 @@ extern "C" int secp256k1_ecdsa_anti_exfil_host_commit_batch_dev(s2k_engine* e, v
     if (!e) return s2k_fail(who, "null engine");
     if (n == 0) return 1;
     if (!commitments_out32 || !rand32) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
     s2c_midstates mid; s2c_tag_midstates(mid);
-    HIPCHK(hipMemsetAsync(commitments_out32, 0, 32 * n, st));
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);
-        hipLaunchKernelGGL(k_s2c_host_commit, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, commitments_out32 + 32 * i0, rand32 + 32 * i0, mid, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    return lanes_run(e, stream, n, {false, false, 0}, {{commitments_out32, 32 * n}}, [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32*) {
+        hipLaunchKernelGGL(k_s2c_host_commit, grid, dim3(256), 0, st, commitments_out32 + 32 * i0, rand32 + 32 * i0, mid, m);
+    });
 }
 extern "C" int secp256k1_ecdsa_anti_exfil_host_commit_batch(s2k_engine* e, unsigned char* commitments_out32, const unsigned char* rand32, size_t n) {
     const char* who = "secp256k1_ecdsa_anti_exfil_host_commit_batch";
@@ -210,12 +161,7 @@ extern "C" int secp256k1_ecdsa_anti_exfil_host_commit_batch(s2k_engine* e, unsig
     memset(commitments_out32, 0, 32 * n);
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    if (!engine_workspace(e, ws_need({32 * n, 32 * n}))) return 0;
-    ws_carver w{e->ws, 0};
-    unsigned char* d_out = w.take<unsigned char>(32 * n); unsigned char* d_in = w.take<unsigned char>(32 * n);
-    HIPCHK(hipMemcpyAsync(d_in, rand32, 32 * n, hipMemcpyHostToDevice, e->stream));
-    if (!secp256k1_ecdsa_anti_exfil_host_commit_batch_dev(e, nullptr, d_out, d_in, n)) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(commitments_out32, d_out, 32 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, commitments_out32, 32 * n}, {rand32, nullptr, 32 * n}};
+    if (!stage_open(e, b)) return 0;
+    return stage_close(e, b, secp256k1_ecdsa_anti_exfil_host_commit_batch_dev(e, nullptr, b[0].at(), b[1].at(), n));
 }

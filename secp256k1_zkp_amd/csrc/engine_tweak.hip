@@ -1,4 +1,4 @@
-#include "engine_internal.h"
+#include "engine_lanes.h"
 #include "tweak.h"
 
 // ------------------------------------------------------------------------------------------------------------
@@ -37,22 +37,12 @@ extern "C" int secp256k1_xonly_pubkey_tweak_add_check_batch_dev(s2k_engine* e, v
     if (n == 0) return 1;
     if (!results || !tweaked32 || !parities || !internal_keys || !tweaks32) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     if (key_format < 0 || key_format > 1) return s2k_fail_arg(who, "key_format must be 0 (x-only, 32 bytes) or 1 (object)");
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    ENGINE_GTAB(e, st);
-    HIPCHK(hipMemsetAsync(results, 0, sizeof(int32_t) * n, st));          // a batch that does not complete never shows an item as valid
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
     const size_t kb = tweak_key_bytes(key_format);
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);
-        hipLaunchKernelGGL(k_tweak_check, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, results + i0, tweaked32 + 32 * i0, parities + i0, internal_keys + kb * i0,
-                           key_format, tweaks32 + 32 * i0, e->gtab, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    return lanes_run(e, stream, n, {true, false, 0}, {{results, sizeof(int32_t) * n}},        // a batch that does not complete never shows an item as valid
+                     [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32*) {
+        hipLaunchKernelGGL(k_tweak_check, grid, dim3(256), 0, st, results + i0, tweaked32 + 32 * i0, parities + i0, internal_keys + kb * i0, key_format,
+                           tweaks32 + 32 * i0, e->gtab, m);
+    });
 }
 extern "C" int secp256k1_xonly_pubkey_tweak_add_check_batch(s2k_engine* e, int32_t* results, const unsigned char* tweaked32, const unsigned char* parities,
                                                             const unsigned char* internal_keys, int key_format, const unsigned char* tweaks32, size_t n) {
@@ -65,18 +55,9 @@ extern "C" int secp256k1_xonly_pubkey_tweak_add_check_batch(s2k_engine* e, int32
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     const size_t kb = tweak_key_bytes(key_format);
-    if (!engine_workspace(e, ws_need({4 * n, 32 * n, n + 64, kb * n, 32 * n}))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n); unsigned char* d_out = w.take<unsigned char>(32 * n); unsigned char* d_par = w.take<unsigned char>(n + 64);
-    unsigned char* d_key = w.take<unsigned char>(kb * n); unsigned char* d_tw = w.take<unsigned char>(32 * n);
-    HIPCHK(hipMemcpyAsync(d_out, tweaked32, 32 * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_par, parities, n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_key, internal_keys, kb * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_tw, tweaks32, 32 * n, hipMemcpyHostToDevice, e->stream));
-    if (!secp256k1_xonly_pubkey_tweak_add_check_batch_dev(e, nullptr, d_res, d_out, d_par, d_key, key_format, d_tw, n)) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n}, {tweaked32, nullptr, 32 * n}, {parities, nullptr, n, 64}, {internal_keys, nullptr, kb * n}, {tweaks32, nullptr, 32 * n}};
+    if (!stage_open(e, b)) return 0;
+    return stage_close(e, b, secp256k1_xonly_pubkey_tweak_add_check_batch_dev(e, nullptr, b[0].at<int32_t>(), b[1].at(), b[2].at(), b[3].at(), key_format, b[4].at(), n));
 }
 
 extern "C" int secp256k1_pubkey_tweak_add_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* pubkeys_out64, const unsigned char* keys,
@@ -86,23 +67,11 @@ extern "C" int secp256k1_pubkey_tweak_add_batch_dev(s2k_engine* e, void* stream,
     if (n == 0) return 1;
     if (!results || !pubkeys_out64 || !keys || !tweaks32) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
     if (key_format < 0 || key_format > 2) return s2k_fail_arg(who, "key_format must be 0 (x-only, 32 bytes), 1 (object) or 2 (compressed)");
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    ENGINE_GTAB(e, st);
-    HIPCHK(hipMemsetAsync(results, 0, sizeof(int32_t) * n, st));          // a batch that does not complete shows no item as tweaked
-    HIPCHK(hipMemsetAsync(pubkeys_out64, 0, 64 * n, st));
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
     const size_t kb = tweak_key_bytes(key_format);
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {
-        const size_t m = std::min(n - i0, e->max_lanes);
-        hipLaunchKernelGGL(k_tweak_add, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, results + i0, pubkeys_out64 + 64 * i0, keys + kb * i0, key_format,
-                           tweaks32 + 32 * i0, e->gtab, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    return lanes_run(e, stream, n, {true, false, 0}, {{results, sizeof(int32_t) * n}, {pubkeys_out64, 64 * n}},      // a batch that does not complete shows no item as tweaked
+                     [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32*) {
+        hipLaunchKernelGGL(k_tweak_add, grid, dim3(256), 0, st, results + i0, pubkeys_out64 + 64 * i0, keys + kb * i0, key_format, tweaks32 + 32 * i0, e->gtab, m);
+    });
 }
 extern "C" int secp256k1_pubkey_tweak_add_batch(s2k_engine* e, int32_t* results, unsigned char* pubkeys_out64, const unsigned char* keys, int key_format,
                                                 const unsigned char* tweaks32, size_t n) {
@@ -115,15 +84,7 @@ extern "C" int secp256k1_pubkey_tweak_add_batch(s2k_engine* e, int32_t* results,
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     const size_t kb = tweak_key_bytes(key_format);
-    if (!engine_workspace(e, ws_need({4 * n, 64 * n, kb * n + 64, 32 * n}))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n); unsigned char* d_pk = w.take<unsigned char>(64 * n); unsigned char* d_key = w.take<unsigned char>(kb * n + 64);
-    unsigned char* d_tw = w.take<unsigned char>(32 * n);
-    HIPCHK(hipMemcpyAsync(d_key, keys, kb * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_tw, tweaks32, 32 * n, hipMemcpyHostToDevice, e->stream));
-    if (!secp256k1_pubkey_tweak_add_batch_dev(e, nullptr, d_res, d_pk, d_key, key_format, d_tw, n)) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(pubkeys_out64, d_pk, 64 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n}, {nullptr, pubkeys_out64, 64 * n}, {keys, nullptr, kb * n, 64}, {tweaks32, nullptr, 32 * n}};
+    if (!stage_open(e, b)) return 0;
+    return stage_close(e, b, secp256k1_pubkey_tweak_add_batch_dev(e, nullptr, b[0].at<int32_t>(), b[1].at(), b[2].at(), key_format, b[3].at(), n));
 }
