@@ -1,4 +1,4 @@
-#include "engine_internal.h"
+#include "engine_lanes.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // Bulletproofs++ norm-argument batch verification (bppp.h)
@@ -206,24 +206,13 @@ extern "C" int secp256k1_bppp_norm_product_verify_batch(s2k_engine* e, int32_t* 
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     const size_t per = std::max<size_t>(1, e->max_lanes / sh.n_terms);
-    const size_t inner = bpv_ws_bytes(std::min(n, per), sh);
-    if (!engine_workspace(e, inner + ws_need({4 * n, n * proof_len + 64, 104 * n, 32 * n, 33 * n_gens, 32 * c_vec_len * n, 33 * n}))) return 0;
-    ws_carver c{e->ws, inner};
-    int32_t* d_res = c.take<int32_t>(n); unsigned char* d_pr = c.take<unsigned char>(n * proof_len + 64); unsigned char* d_tr = c.take<unsigned char>(104 * n);
-    unsigned char* d_rho = c.take<unsigned char>(32 * n); unsigned char* d_g33 = c.take<unsigned char>(33 * n_gens);
-    unsigned char* d_cv = c.take<unsigned char>(32 * c_vec_len * n); unsigned char* d_cm = c.take<unsigned char>(33 * n);
-    hipStream_t st = e->stream;
-    stream_guard sg(e, st);
-    HIPCHK(hipMemcpyAsync(d_pr, proofs, n * proof_len, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_tr, transcripts, 104 * n, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_rho, rho, 32 * n, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_g33, gens33, 33 * n_gens, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_cv, c_vec, 32 * c_vec_len * n, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_cm, commits33, 33 * n, hipMemcpyHostToDevice, st));
-    if (!secp256k1_bppp_norm_product_verify_batch_dev(e, nullptr, d_res, d_pr, proof_len, d_tr, d_rho, d_g33, gens33, n_gens, g_len, d_cv, c_vec_len, d_cm, n)) return 0;
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
+    stream_guard sg(e, e->stream);
+    // the `_dev` form carves its launch groups from offset 0: the buffers lie behind
+    stage_buf b[] = {{nullptr, results, 4 * n}, {proofs, nullptr, n * proof_len, 64}, {transcripts, nullptr, 104 * n}, {rho, nullptr, 32 * n}, {gens33, nullptr, 33 * n_gens},
+                     {c_vec, nullptr, 32 * c_vec_len * n}, {commits33, nullptr, 33 * n}};
+    if (!stage_open(e, b, bpv_ws_bytes(std::min(n, per), sh))) return 0;
+    return stage_close(e, b, secp256k1_bppp_norm_product_verify_batch_dev(e, nullptr, b[0].at<int32_t>(), b[1].at(), proof_len, b[2].at(), b[3].at(), b[4].at(), gens33, n_gens, g_len,
+                                                                          b[5].at(), c_vec_len, b[6].at(), n));
 }
 
 // ---- secp256k1_bppp_commit, batched (bppp.h) ------------------------------------------------------------------------------------
@@ -330,23 +319,11 @@ extern "C" int secp256k1_bppp_commit_batch(s2k_engine* e, unsigned char* commits
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     const size_t per = std::max<size_t>(1, e->max_lanes / (n_gens + 1));
-    const size_t io = ws_need({33 * n, 4 * n, 33 * n_gens, 32 * g_len * n, 32 * h_len * n, 32 * h_len * n, 32 * n});
-    if (!engine_workspace(e, bpc_ws_bytes(std::min(n, per), n_gens) + io)) return 0;
-    hipStream_t st = e->stream;
-    stream_guard sg(e, st);
-    ws_carver c0{e->ws, bpc_ws_bytes(std::min(n, per), n_gens)};
-    unsigned char* d_out = c0.take<unsigned char>(33 * n); int32_t* d_res = c0.take<int32_t>(n); unsigned char* d_g33 = c0.take<unsigned char>(33 * n_gens);
-    unsigned char* d_nv = c0.take<unsigned char>(32 * g_len * n); unsigned char* d_lv = c0.take<unsigned char>(32 * h_len * n);
-    unsigned char* d_cv = c0.take<unsigned char>(32 * h_len * n); unsigned char* d_mu = c0.take<unsigned char>(32 * n);
-    HIPCHK(hipMemcpyAsync(d_g33, gens33, 33 * n_gens, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_nv, n_vec, 32 * g_len * n, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_lv, l_vec, 32 * h_len * n, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_cv, c_vec, 32 * h_len * n, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_mu, mu, 32 * n, hipMemcpyHostToDevice, st));
-    if (!secp256k1_bppp_commit_batch_dev(e, nullptr, d_out, d_res, d_g33, gens33, n_gens, g_len, d_nv, d_lv, d_cv, h_len, d_mu, n)) return 0;
-    HIPCHK(hipMemcpyAsync(commits33, d_out, 33 * n, hipMemcpyDeviceToHost, st));
-    if (results) HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
+    stream_guard sg(e, e->stream);
+    stage_buf b[] = {{nullptr, commits33, 33 * n}, {nullptr, results, 4 * n}, {gens33, nullptr, 33 * n_gens}, {n_vec, nullptr, 32 * g_len * n}, {l_vec, nullptr, 32 * h_len * n},
+                     {c_vec, nullptr, 32 * h_len * n}, {mu, nullptr, 32 * n}};
+    if (!stage_open(e, b, bpc_ws_bytes(std::min(n, per), n_gens))) return 0;
+    return stage_close(e, b, secp256k1_bppp_commit_batch_dev(e, nullptr, b[0].at(), b[1].at<int32_t>(), b[2].at(), gens33, n_gens, g_len, b[3].at(), b[4].at(),
+                                                             b[5].at(), h_len, b[6].at(), n));
 }
 

@@ -1,4 +1,4 @@
-#include "engine_internal.h"
+#include "engine_verdict.h"
 #include "bppp_all.h"
 
 // ------------------------------------------------------------------------------------------------------------
@@ -34,13 +34,6 @@ k_ba_sg(u32* term_sc, const u32* sg_factors, const int* proof_ok, bp_shape sh, s
     const size_t p = t / (sh.g_len - 1); const u32 i = 1u + (u32)(t % (sh.g_len - 1));
     if (p >= n || !proof_ok[p]) return;
     bp_sg_entry(term_sc + p * sh.n_terms * 8, sg_factors + p * (8 * BP_MAX_LOG_G), sh, i);
-}
-__global__ void __launch_bounds__(256)
-k_ba_node(u32* out, const u32* __restrict__ in, sa_midstates mid, size_t cnt_in, size_t cnt_out) {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= cnt_out) return;
-    const size_t left = cnt_in - SA_FANIN * j;
-    sa_node(out + 8 * j, mid, in + 8 * SA_FANIN * j, left < SA_FANIN ? (u32)left : SA_FANIN);
 }
 struct ba_gd { u32 w[8]; };
 __global__ void k_ba_seed(u32* seed8, unsigned char* seed32_out, sa_midstates mid, ba_gd gd, const u32* root8, u64 n, u64 proof_len, u64 h_len) {
@@ -84,10 +77,6 @@ k_ba_own_scalars(unsigned char* sc, bp_shape sh, u32 own, const u32* __restrict_
     if (p >= n) return;
     ba_own_scalar(sc + 32 * ((size_t)sh.n_gens + t), sh, (u32)(t % own), term_sc + p * sh.n_terms * 8, zp + 8 * p);
 }
-__global__ void k_ba_final(int32_t* verdict, const u32* flags, const u32* res28) {
-    if (threadIdx.x || blockIdx.x) return;
-    *verdict = (flags[0] == 0u) && (res28[27] != 0u);
-}
 static size_t ba_own_terms(const bp_shape& sh) { return 2 * (size_t)sh.n_rounds + 1; }
 static size_t ba_msm_points(const bp_shape& sh, size_t n) { return (size_t)sh.n_gens + n * ba_own_terms(sh); }
 // n >= 1
@@ -100,15 +89,15 @@ static const sa_midstates& ba_mid() { static const sa_midstates m = [] { sa_mids
 // device pointers in, verdict to d_verdict[0] and (when asked for) the seed to d_seed_out; n >= 1, a shape bp_make_shape accepts with log_g <= BP_MAX_LOG_G,
 // n_gens + n (2 n_rounds + 1) <= msm_max_terms.
 // Timing: ev[0] .. ev_ba[0] the per-proof scalars and the item digests; .. ev_ba[1] the tree, the seed and z'; .. ev[2] the column sums,
-// the own terms' scalars and whatever is left of the points on the side stream; ev[2] .. ev[3] the MSM (ev_ba[2], ev_ba[3]: stand-ins while msm_launch records around its own dominant kernel, as in sa_launch); ev[1] the end.
+// the own terms' scalars and whatever is left of the points on the side stream; ev[2] .. ev[3] the MSM; ev[1] the end (verdict_tail).
 static int ba_launch(s2k_engine* e, hipStream_t st, ws_carver& c, int32_t* d_verdict, unsigned char* d_seed_out, const bp_shape& sh, const unsigned char* d_pr, size_t proof_len,
                      const unsigned char* d_tr, const unsigned char* d_rho, const unsigned char* d_g33, const unsigned char* gens33_host, const unsigned char* d_cv,
                      const unsigned char* d_cm, size_t n) {
-    for (int k = 0; k < 4; k++) if (!e->ev_ba[k]) HIPCHK(hipEventCreate(&e->ev_ba[k]));
+    if (!verdict_events(e->ev_ba)) return 0;
     const size_t own = ba_own_terms(sh), M = ba_msm_points(sh, n);
     const u32 ncols = sh.n_gens + 1u;
-    size_t counts[SA_MAX_LEVELS], ccounts[SA_MAX_LEVELS]; u32 chunk_len;
-    const int levels = sa_level_plan(counts, n), cpasses = ba_colsum_plan(ccounts, &chunk_len, n);
+    size_t ccounts[SA_MAX_LEVELS]; u32 chunk_len;
+    const int cpasses = ba_colsum_plan(ccounts, &chunk_len, n);
     u32* term_sc = c.take<u32>(n * sh.n_terms * 8); u32* sg_factors = c.take<u32>(n * 8 * BP_MAX_LOG_G);
     u32* d_nodes = c.take<u32>(sa_node_count(n) * 8 + 16); int* proof_ok = c.take<int>(n + 16); u32* d_zp = c.take<u32>(8 * n + 16);
     u32* d_part = c.take<u32>(ba_colsum_rows(n) * ncols * 8 + 16);
@@ -128,13 +117,8 @@ static int ba_launch(s2k_engine* e, hipStream_t st, ws_carver& c, int32_t* d_ver
     hipLaunchKernelGGL(k_ba_proofs, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, term_sc, sg_factors, d_nodes, proof_ok, d_flags, mid, sh, d_pr, proof_len, d_tr, d_rho, d_cv, d_cm, n);
     if (sh.g_len > 1) hipLaunchKernelGGL(k_ba_sg, dim3((unsigned)((n * (sh.g_len - 1) + 255) / 256)), dim3(256), 0, st, term_sc, (const u32*)sg_factors, (const int*)proof_ok, sh, n);
     HIPCHK(hipEventRecord(e->ev_ba[0], st));
-    u32* level = d_nodes;
-    for (int k = 0; k + 1 < levels; k++) {
-        u32* next = level + 8 * counts[k];
-        hipLaunchKernelGGL(k_ba_node, dim3((unsigned)((counts[k + 1] + 255) / 256)), dim3(256), 0, st, next, (const u32*)level, mid, counts[k], counts[k + 1]);
-        level = next;
-    }
-    hipLaunchKernelGGL(k_ba_seed, dim3(1), dim3(64), 0, st, d_seed, d_seed_out, mid, gd, (const u32*)level, (u64)n, (u64)proof_len, (u64)sh.h_len);
+    const u32* root = verdict_tree(st, d_nodes, mid, n);
+    hipLaunchKernelGGL(k_ba_seed, dim3(1), dim3(64), 0, st, d_seed, d_seed_out, mid, gd, root, (u64)n, (u64)proof_len, (u64)sh.h_len);
     hipLaunchKernelGGL(k_ba_coeff, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_zp, mid, (const u32*)d_seed, n);
     HIPCHK(hipEventRecord(e->ev_ba[1], st));
     // S_t and g_sc: one pass over chunks of proofs, then partial sums with fan-in 16; the pass that leaves one row writes the sum's scalars
@@ -151,18 +135,7 @@ static int ba_launch(s2k_engine* e, hipStream_t st, ws_carver& c, int32_t* d_ver
     hipLaunchKernelGGL(k_ba_own_scalars, dim3((unsigned)((n * own + 255) / 256)), dim3(256), 0, st, d_sc, sh, (u32)own, (const u32*)term_sc, (const u32*)d_zp, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamWaitEvent(st, e->ev_msm_join, 0));
-    HIPCHK(hipEventRecord(e->ev[2], st));
-    u32* res28 = nullptr;
-    hipEvent_t const keep2 = e->ev[2], keep3 = e->ev[3];
-    e->ev[2] = e->ev_ba[2]; e->ev[3] = e->ev_ba[3];
-    const int ok = msm_launch(e, st, c, &res28, d_gsc, d_sc, d_pts, d_inf, M);
-    e->ev[2] = keep2; e->ev[3] = keep3;
-    if (!ok) return 0;
-    HIPCHK(hipEventRecord(e->ev[3], st));
-    hipLaunchKernelGGL(k_ba_final, dim3(1), dim3(64), 0, st, d_verdict, (const u32*)d_flags, (const u32*)res28);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    return verdict_tail(e, st, c, e->ev_ba, d_verdict, d_flags, d_gsc, d_sc, d_pts, d_inf, M);
 }
 // more points than one sum indexes, or more bytes than a call indexes
 static int ba_size_ok(const char* who, const s2k_engine* e, const bp_shape& sh, size_t n) {
@@ -186,12 +159,7 @@ extern "C" int secp256k1_bppp_norm_product_verify_all_dev(s2k_engine* e, void* s
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
     stream_guard sg(e, st);
-    if (!shape_ok) {                                           // n == 0: nothing to refuse, verdict 1; a shape the reference refuses (:446-461): verdict 0; the seed 32 zero bytes
-        launch_set_word(st, (u32*)verdict_dev, n ? 0u : 1u);
-        HIPCHK(hipGetLastError());
-        if (seed32_out_dev) HIPCHK(hipMemsetAsync(seed32_out_dev, 0, 32, st));
-        return 1;
-    }
+    if (!shape_ok) return verdict_reply(st, verdict_dev, seed32_out_dev, n ? 0u : 1u);      // n == 0: nothing to refuse; a shape the reference refuses (:446-461): verdict 0
     if (!engine_workspace(e, ba_ws_bytes(e, sh, n))) return 0;
     ws_carver c{e->ws, 0};
     return ba_launch(e, st, c, verdict_dev, seed32_out_dev, sh, proofs, proof_len, transcripts, rho, gens33_dev, gens33_host, c_vec, commits33, n);
@@ -219,43 +187,17 @@ extern "C" int secp256k1_bppp_norm_product_verify_all(s2k_engine* e, int32_t* ve
     // uploads behind both, so that it neither reallocates nor overwrites them.
     const size_t per = std::max<size_t>(1, e->max_lanes / sh.n_terms);
     const size_t front = std::max(ba_ws_bytes(e, sh, n), results ? bpv_ws_bytes(std::min(n, per), sh) : (size_t)0);
-    if (!engine_workspace(e, front + ws_need({n * proof_len + 64, 104 * n, 32 * n, 33 * n_gens, 32 * c_vec_len * n, 33 * n, 4 * n + 64, 64, 16}))) return 0;
-    ws_carver c0{e->ws, front};
-    unsigned char* d_pr = c0.take<unsigned char>(n * proof_len + 64); unsigned char* d_tr = c0.take<unsigned char>(104 * n); unsigned char* d_rho = c0.take<unsigned char>(32 * n);
-    unsigned char* d_g33 = c0.take<unsigned char>(33 * n_gens); unsigned char* d_cv = c0.take<unsigned char>(32 * c_vec_len * n); unsigned char* d_cm = c0.take<unsigned char>(33 * n);
-    int32_t* d_res = c0.take<int32_t>(n + 16); unsigned char* d_seed = c0.take<unsigned char>(64); int32_t* d_verdict = c0.take<int32_t>(4);
-    hipStream_t st = e->stream;
-    {
-        stream_guard sg(e, st);
-        HIPCHK(hipMemcpyAsync(d_pr, proofs, n * proof_len, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_tr, transcripts, 104 * n, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_rho, rho, 32 * n, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_g33, gens33, 33 * n_gens, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_cv, c_vec, 32 * c_vec_len * n, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_cm, commits33, 33 * n, hipMemcpyHostToDevice, st));
-        ws_carver c{e->ws, 0};
-        if (!ba_launch(e, st, c, d_verdict, seed32_out ? d_seed : nullptr, sh, d_pr, proof_len, d_tr, d_rho, d_g33, gens33, d_cv, d_cm, n)) return 0;
-        HIPCHK(hipMemcpyAsync(verdict, d_verdict, 4, hipMemcpyDeviceToHost, st));
-        if (seed32_out) HIPCHK(hipMemcpyAsync(seed32_out, d_seed, 32, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    if (!results) return 1;
-    if (*verdict) { for (size_t i = 0; i < n; i++) results[i] = 1; return 1; }
-    if (!secp256k1_bppp_norm_product_verify_batch_dev(e, nullptr, d_res, d_pr, proof_len, d_tr, d_rho, d_g33, gens33, n_gens, g_len, d_cv, c_vec_len, d_cm, n)) return 0;
-    HIPCHK(hipMemcpyAsync(results, d_res, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
+    const stage_buf in[] = {{proofs, nullptr, n * proof_len, 64}, {transcripts, nullptr, 104 * n}, {rho, nullptr, 32 * n}, {gens33, nullptr, 33 * n_gens},
+                            {c_vec, nullptr, 32 * c_vec_len * n}, {commits33, nullptr, 33 * n}};
+    return verdict_host(e, in, front, verdict, results, seed32_out, n,
+        [&](hipStream_t st, ws_carver& c, int32_t* d_verdict, unsigned char* d_seed, const stage_buf* b) {
+            return ba_launch(e, st, c, d_verdict, d_seed, sh, b[0].at(), proof_len, b[1].at(), b[2].at(), b[3].at(), gens33, b[4].at(), b[5].at(), n); },
+        [&](int32_t* d_res, const stage_buf* b) {
+            return secp256k1_bppp_norm_product_verify_batch_dev(e, nullptr, d_res, b[0].at(), proof_len, b[1].at(), b[2].at(), b[3].at(), gens33, n_gens, g_len, b[4].at(), c_vec_len,
+                                                                b[5].at(), n); });
 }
 // The phases of the most recent verify_all call of this engine, in ms, once its work is complete (s2k_engine_sync): [0] generators, per-proof
 // scalars and item digests, [1] hash tree, seed and z', [2] column sums and own terms, [3] the MSM.  -1 where no such call has run.
 extern "C" int s2k_bppp_all_last_split_ms(s2k_engine* e, float* out4) {
-    if (!e) return s2k_fail("s2k_bppp_all_last_split_ms", "null engine");
-    if (!out4) return s2k_fail_arg("s2k_bppp_all_last_split_ms", "illegal argument");
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    HIPCHK(hipSetDevice(e->device));
-    for (int k = 0; k < 4; k++) out4[k] = -1.0f;
-    if (!e->ev_ba[0] || !e->ev_ba[1]) return 1;
-    hipEvent_t const b[5] = {e->ev[0], e->ev_ba[0], e->ev_ba[1], e->ev[2], e->ev[3]};
-    for (int k = 0; k < 4; k++) if (hipEventElapsedTime(&out4[k], b[k], b[k + 1]) != hipSuccess) { (void)hipGetLastError(); out4[k] = -1.0f; }
-    return 1;
+    return verdict_split_ms("s2k_bppp_all_last_split_ms", e, &s2k_engine::ev_ba, out4);
 }

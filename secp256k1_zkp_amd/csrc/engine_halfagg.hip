@@ -1,4 +1,4 @@
-#include "engine_internal.h"
+#include "engine_verdict.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // half-aggregated Schnorr signatures (halfagg.h): one (2n+1)-term MSM per aggregate
@@ -63,10 +63,6 @@ k_ha_scalars(unsigned char* sc, unsigned char* g32, u32* flags, const u32* state
     if (i == 0 && !ha_gscalar(g32, aggsig + 32 * n)) flags[0] = 1u;
     if (i < n) ha_scalars(sc + 64 * i, states, bip340, aggsig, pkx32, msgs32, i);
 }
-__global__ void k_ha_final(int32_t* result, const u32* flags, const u32* res28) {
-    if (threadIdx.x || blockIdx.x) return;
-    *result = (flags[0] == 0u) && (res28[27] != 0u);
-}
 size_t ha_ws_bytes(const s2k_engine* e, size_t n) {
     const size_t nblocks = (3 * n) >> 1, nt = 2 * n + 1;
     return ws_need({128 * n + 64, 32 * n + 64, nblocks * 256 + 64, nblocks * 32 + 64, 64 * n + 64, 64, 64, 16}) + msm_ws_bytes(e, nt + 1, engine_msm_plan(e, nt));
@@ -129,7 +125,7 @@ int ha_launch(s2k_engine* e, hipStream_t st, ws_carver& c, int32_t* d_res, const
     u32* res28 = nullptr;
     // the MSM's points are R_0, P_0, R_1, P_1, ... with scalars z_0, z_0 e_0, z_1, z_1 e_1, ...; the generator term carries -s
     if (!msm_launch(e, st, c, &res28, d_g, d_sc, d_pts, nullptr, 2 * n)) return 0;
-    hipLaunchKernelGGL(k_ha_final, dim3(1), dim3(64), 0, st, d_res, d_flags, res28);
+    hipLaunchKernelGGL(k_verdict_final<>, dim3(1), dim3(64), 0, st, d_res, (const u32*)d_flags, (const u32*)res28);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev[1], st));
     return 1;
@@ -187,24 +183,14 @@ extern "C" int secp256k1_schnorrsig_aggverify_amd(s2k_engine* e, int32_t* result
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     const size_t pkb = pk_format ? 64 : 32;
-    const size_t io = ws_need({pkb * n + 64, 32 * n + 64, 32 * (n + 1), 16});
-    if (!engine_workspace(e, ha_ws_bytes(e, n) + io)) return 0;
-    ws_carver c0{e->ws, ha_ws_bytes(e, n)};
-    unsigned char* d_pk = c0.take<unsigned char>(pkb * n + 64); unsigned char* d_msg = c0.take<unsigned char>(32 * n + 64);
-    unsigned char* d_agg = c0.take<unsigned char>(32 * (n + 1)); int32_t* d_res = c0.take<int32_t>(4);
     hipStream_t st = e->stream;
     stream_guard sg(e, st);
-    if (n) {
-        HIPCHK(hipMemcpyAsync(d_pk, pubkeys, pkb * n, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_msg, msgs32, 32 * n, hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(hipMemcpyAsync(d_agg, aggsig, 32 * (n + 1), hipMemcpyHostToDevice, st));
+    // the device part at 0, the buffers behind it
+    stage_buf b[] = {{pubkeys, nullptr, pkb * n, 64}, {msgs32, nullptr, 32 * n, 64}, {aggsig, nullptr, 32 * (n + 1)}, {nullptr, result, 4, 12}};
+    if (!stage_open(e, b, ha_ws_bytes(e, n))) return 0;
     ws_carver c{e->ws, 0};
     const int host_chain = e->halfagg_host_chain;      // S2K_OPT_HALFAGG_HOST_CHAIN 0: the device chain (same verdicts; tests)
     const ha_host_src hsrc{aggsig, pubkeys, pk_format, msgs32};
-    if (!ha_launch(e, st, c, d_res, d_pk, pk_format, d_msg, n, d_agg, host_chain ? &hsrc : nullptr)) return 0;
-    HIPCHK(hipMemcpyAsync(result, d_res, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
+    return stage_close(e, b, ha_launch(e, st, c, b[3].at<int32_t>(), b[0].at(), pk_format, b[1].at(), n, b[2].at(), host_chain ? &hsrc : nullptr));
 }
 

@@ -1,4 +1,4 @@
-#include "engine_internal.h"
+#include "engine_lanes.h"
 #include "halfagg_batch.h"
 
 // ------------------------------------------------------------------------------------------------------------
@@ -64,7 +64,7 @@ static size_t hab_verify_carve_bytes(const hab_verify_sizes& z) {
     return ws_need({8 * 3 * (z.K + 1), 4 * z.NP + 64, 128 * z.NT + 64, 64 * z.NT + 64, 32 * z.K + 64, 32 * z.N + 64, 32 * (hab_state_slot(z.N) + 1), 4 * z.K + 64, 64 * z.K + 64,
                     4 * z.K + 64}) + 256;      // (+ 256: what follows starts at the next 256-byte boundary)
 }
-// workspace of one call behind `front` bytes of staged inputs, sized once (growing the workspace moves it)
+// workspace of one call, behind the staged inputs where the host form runs it
 static size_t hab_verify_ws(const s2k_engine* e, const hab_verify_sizes& z, const hab_verify_plan& p, const uint64_t* item_off) {
     size_t tail = mm_ws_bytes(e, p.moff.data(), z.K, 1u);
     for (u32 k : p.large) tail = std::max(tail, ha_ws_bytes(e, (size_t)(item_off[k + 1] - item_off[k])));
@@ -146,17 +146,9 @@ extern "C" int secp256k1_schnorrsig_aggverify_batch(s2k_engine* e, int32_t* resu
     stream_guard sg(e, st);
     const size_t K = n_aggs, N = (size_t)item_off[K], A = (size_t)aggsig_off[K], pkb = pk_format ? 64 : 32;
     const hab_verify_plan p = hab_plan_verify(item_off, aggsig_off, K, MM_MAX_TERMS);
-    const size_t front = ws_need({pkb * N + 64, 32 * N + 64, A + 64, 4 * K + 64});
-    if (!engine_workspace(e, front + hab_verify_ws(e, hab_sizes(item_off, K, p), p, item_off))) return 0;
-    ws_carver c{e->ws, 0};
-    unsigned char* d_pk = c.take<unsigned char>(pkb * N + 64); unsigned char* d_msg = c.take<unsigned char>(32 * N + 64); unsigned char* d_agg = c.take<unsigned char>(A + 64);
-    int32_t* d_res = c.take<int32_t>(K + 16);
-    if (N) { HIPCHK(hipMemcpyAsync(d_pk, pubkeys, pkb * N, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(d_msg, msgs32, 32 * N, hipMemcpyHostToDevice, st)); }
-    if (A) HIPCHK(hipMemcpyAsync(d_agg, aggsigs, A, hipMemcpyHostToDevice, st));
-    if (!hab_verify_run(e, st, front, d_res, d_pk, pk_format, d_msg, d_agg, item_off, aggsig_off, K, p)) { (void)hipStreamSynchronize(st); return 0; }
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * K, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
+    stage_buf b[] = {{pubkeys, nullptr, pkb * N, 64}, {msgs32, nullptr, 32 * N, 64}, {aggsigs, nullptr, A, 64}, {nullptr, results, 4 * K, 64}};
+    if (!stage_open(e, b, 0, hab_verify_ws(e, hab_sizes(item_off, K, p), p, item_off))) return 0;
+    return stage_close(e, b, hab_verify_run(e, st, stage_bytes(b), b[3].at<int32_t>(), b[0].at(), pk_format, b[1].at(), b[2].at(), item_off, aggsig_off, K, p));
 }
 
 // ---- aggregation -------------------------------------------------------------------------------------------------------------------------
@@ -244,20 +236,11 @@ static int hab_agg_host(const char* who, int inc, s2k_engine* e, int32_t* result
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = e->stream;
     stream_guard sg(e, st);
-    const size_t N = p.N, pkb = pk_format ? 64 : 32, ob = 32 * (N + K);
-    const size_t front = ws_need({4 * K + 64, ob + 64, p.in_bytes + 64, pkb * N + 64, 32 * N + 64, 64 * p.n_new + 64});
-    if (!engine_workspace(e, front + hab_agg_ws(p))) return 0;
-    ws_carver c{e->ws, 0};
-    int32_t* d_res = c.take<int32_t>(K + 16); unsigned char* d_out = c.take<unsigned char>(ob + 64); unsigned char* d_in = c.take<unsigned char>(p.in_bytes + 64);
-    unsigned char* d_pk = c.take<unsigned char>(pkb * N + 64); unsigned char* d_msg = c.take<unsigned char>(32 * N + 64); unsigned char* d_new = c.take<unsigned char>(64 * p.n_new + 64);
-    if (p.in_bytes) HIPCHK(hipMemcpyAsync(d_in, aggsigs_in, p.in_bytes, hipMemcpyHostToDevice, st));
-    if (N) { HIPCHK(hipMemcpyAsync(d_pk, pks, pkb * N, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(d_msg, msgs32, 32 * N, hipMemcpyHostToDevice, st)); }
-    if (p.n_new) HIPCHK(hipMemcpyAsync(d_new, new_sigs64, 64 * p.n_new, hipMemcpyHostToDevice, st));
-    if (!hab_agg_run(e, st, front, d_res, d_out, d_in, inc, d_pk, pk_format, d_msg, d_new, p)) { (void)hipStreamSynchronize(st); return 0; }
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * K, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
+    const size_t N = p.N, pkb = pk_format ? 64 : 32;
+    stage_buf b[] = {{nullptr, results, 4 * K, 64}, {nullptr, out, 32 * (N + K), 64}, {aggsigs_in, nullptr, p.in_bytes, 64}, {pks, nullptr, pkb * N, 64},
+                     {msgs32, nullptr, 32 * N, 64}, {new_sigs64, nullptr, 64 * p.n_new, 64}};
+    if (!stage_open(e, b, 0, hab_agg_ws(p))) return 0;
+    return stage_close(e, b, hab_agg_run(e, st, stage_bytes(b), b[0].at<int32_t>(), b[1].at(), b[2].opt(), inc, b[3].at(), pk_format, b[4].at(), b[5].opt(), p));
 }
 extern "C" int secp256k1_schnorrsig_inc_aggregate_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* aggsigs_out, const unsigned char* aggsigs_in,
                                                             const uint64_t* n_before, const unsigned char* pubkeys, int pk_format, const unsigned char* msgs32,

@@ -22,10 +22,14 @@
 //   engine_ellswift.hip    ElligatorSwift decoding and encoding of public keys (ellswift.h)
 //   engine_schnorr_all.hip one-verdict batch verification of BIP-340 signatures as a single multi-scalar multiplication (schnorr_all.h)
 //   engine_bppp_all.hip    one-verdict batch verification of BP++ norm arguments over one generator set as a single multi-scalar multiplication (bppp_all.h)
-// What every one-item-per-lane family does around its kernel is engine_lanes.h (host code only, included by the units that use it):
-// lanes_run behind the `_dev` forms, stage_open / stage_close behind the host-buffer forms, der_window for DER-packed signatures; the
-// `_group` forms that split a batch by items go through group_by_items (engine_core.hip).  The families with a workspace of their own
-// (MSM, rangeproof, BP++, half-aggregates, whitelist, the one-verdict verifiers, MuSig aggregation) carve it by hand: ws_carver / ws_need below.
+// What a family does around its kernels is engine_lanes.h (host code only, included by the units that use it): lanes_run behind the
+// `_dev` forms of the one-item-per-lane families, stage_open / stage_close behind the host-buffer forms of every family but MSM and
+// rangeproof (each staged buffer named once, beside the device part's own workspace where there is one), der_window for DER-packed
+// signatures; the `_group` forms that split a batch by items go through group_by_items (engine_core.hip).  What the verifiers that answer
+// a batch with one verdict share (engine_schnorr_all, engine_bppp_all, the final kernel also engine_halfagg) is engine_verdict.h: the hash
+// tree's node kernel and level loop, the MSM behind stand-in events, the final kernel, the split times and the host sequence.  The families
+// with a workspace of their own (MSM, rangeproof, BP++, half-aggregates, whitelist, the one-verdict verifiers, MuSig aggregation) carve
+// the device part's scratch by hand inside their runners: ws_carver / ws_need below.
 // The per-lane arithmetic lives in the headers next to these files.  No device function is called across translation units (no -fgpu-rdc):
 // a family that needs another family's kernels calls the HOST function that launches them.
 // There is no CPU implementation behind the entry points: without a HIP device every call fails loudly.

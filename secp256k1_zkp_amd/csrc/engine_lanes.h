@@ -1,6 +1,7 @@
-// engine_lanes.h -- what every one-item-per-lane family does around its kernel, written once (host code only):
-//   lanes_run               the `_dev` form: device, lock, stream, tables, zeroed outputs, events, the sub-range loop
-//   stage_open / _close     the host-buffer form: every buffer named once, carved from the workspace, uploaded, downloaded
+// engine_lanes.h -- what a family does around its kernels, written once (host code only):
+//   lanes_run               the `_dev` form of a one-item-per-lane family: device, lock, stream, tables, zeroed outputs, events, the sub-range loop
+//   stage_open / _close     the host-buffer form of every family: each buffer named once, carved from the workspace (beside the device part's
+//                           own workspace, where it has one), uploaded, downloaded
 //   der_window              the bytes and rebased offsets of a DER-packed signature array
 // An entry point keeps its own prologue (who, null engine, n == 0, ARG_CHECK, formats) and hands the rest to these.
 #pragma once
@@ -54,13 +55,23 @@ struct stage_buf {
     template <class T = unsigned char> T* at() const { return (T*)dev; }
     template <class T = unsigned char> T* opt() const { return in ? (T*)dev : nullptr; }
 };
-// sizes the workspace (the ws_need rule over bytes + pad), carves the buffers in order from offset 0 and queues the uploads on e->stream
+// where the last buffer ends when the first one starts at a 256-byte boundary
 template <size_t N>
-static int stage_open(s2k_engine* e, stage_buf (&b)[N]) {
-    size_t total = 0;
-    for (const stage_buf& s : b) total = ((total + 255) & ~size_t(255)) + s.bytes + s.pad;
-    if (!engine_workspace(e, total + 256)) return 0;
-    ws_carver w{e->ws, 0};
+static size_t stage_end(const stage_buf (&b)[N]) {
+    size_t t = 0;
+    for (const stage_buf& s : b) t = ((t + 255) & ~size_t(255)) + s.bytes + s.pad;
+    return t;
+}
+// the staged size (the ws_need rule over bytes + pad): with the buffers at offset 0, where a carve behind them starts
+template <size_t N>
+static size_t stage_bytes(const stage_buf (&b)[N]) { return (stage_end(b) + 255) & ~size_t(255); }
+// sizes the workspace, carves the buffers in order from offset lo and queues the uploads on e->stream.  A form whose device part has a
+// workspace of its own says where it lies: in front of the buffers ([0, lo): the carves that start at 0 again, such as a locating call's)
+// or behind them (extra bytes from stage_bytes(b) on; lo = 0).
+template <size_t N>
+static int stage_open(s2k_engine* e, stage_buf (&b)[N], size_t lo = 0, size_t extra = 0) {
+    if (!engine_workspace(e, lo + stage_end(b) + 256 + extra)) return 0;      // (sized once: growing the workspace moves it)
+    ws_carver w{e->ws, lo};
     for (stage_buf& s : b) s.dev = w.take<unsigned char>(s.bytes + s.pad);
     for (const stage_buf& s : b) if (s.in && s.bytes) HIPCHK(hipMemcpyAsync(s.dev, s.in, s.bytes, hipMemcpyHostToDevice, e->stream));
     return 1;

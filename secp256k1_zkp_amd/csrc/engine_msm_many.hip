@@ -1,4 +1,4 @@
-#include "engine_internal.h"
+#include "engine_lanes.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // K independent multi-scalar multiplications in ONE launch chain (s2k_ecmult_multi_many[_dev])
@@ -290,24 +290,12 @@ extern "C" int s2k_ecmult_multi_many(s2k_engine* e, unsigned char* r_xy, int32_t
     memset(r_inf, 0, sizeof(int32_t) * K);
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    const size_t front = ws_need({32 * n + 64, 64 * n + 64, n + 64, 32 * K + 64, 64 * K + 64, 4 * K + 64});
     hipStream_t st = e->stream;
     stream_guard sg(e, st);
-    if (!engine_workspace(e, front + mm_ws_bytes(e, offsets, K, g_sc ? 1u : 0u))) return 0;      // (sized once: growing the workspace moves it)
-    ws_carver c{e->ws, 0};
-    unsigned char* d_sc = c.take<unsigned char>(32 * n + 64); unsigned char* d_pt = c.take<unsigned char>(64 * n + 64); unsigned char* d_inf = c.take<unsigned char>(n + 64);
-    unsigned char* d_g = c.take<unsigned char>(32 * K + 64); unsigned char* d_r = c.take<unsigned char>(64 * K + 64); int32_t* d_ri = c.take<int32_t>(K + 16);
-    if (n) {
-        HIPCHK(hipMemcpyAsync(d_sc, sc, 32 * n, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_pt, pt_xy, 64 * n, hipMemcpyHostToDevice, st));
-        if (pt_inf) HIPCHK(hipMemcpyAsync(d_inf, pt_inf, n, hipMemcpyHostToDevice, st));
-    }
-    if (g_sc) HIPCHK(hipMemcpyAsync(d_g, g_sc, 32 * K, hipMemcpyHostToDevice, st));
+    stage_buf b[] = {{sc, nullptr, 32 * n, 64}, {pt_xy, nullptr, 64 * n, 64}, {pt_inf, nullptr, n, 64}, {g_sc, nullptr, 32 * K, 64}, {nullptr, r_xy, 64 * K, 64}, {nullptr, r_inf, 4 * K, 64}};
+    if (!stage_open(e, b, 0, mm_ws_bytes(e, offsets, K, g_sc ? 1u : 0u))) return 0;
     HIPCHK(hipEventRecord(e->ev[0], st));
-    if (!mm_impl(e, st, front, d_r, d_ri, g_sc ? d_g : nullptr, d_sc, d_pt, pt_inf ? d_inf : nullptr, offsets, K)) return 0;
-    HIPCHK(hipEventRecord(e->ev[1], st));
-    HIPCHK(hipMemcpyAsync(r_xy, d_r, 64 * K, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(r_inf, d_ri, 4 * K, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
+    const int ok = mm_impl(e, st, stage_bytes(b), b[4].at(), b[5].at<int32_t>(), b[3].opt(), b[0].at(), b[1].at(), b[2].opt(), offsets, K);
+    if (ok) HIPCHK(hipEventRecord(e->ev[1], st));
+    return stage_close(e, b, ok);
 }

@@ -1,4 +1,4 @@
-#include "engine_internal.h"
+#include "engine_lanes.h"
 #include "musig_agg.h"
 
 // ------------------------------------------------------------------------------------------------------------
@@ -206,17 +206,10 @@ extern "C" int secp256k1_musig_pubkey_agg_batch(s2k_engine* e, int32_t* results,
     stream_guard sg(e, e->stream);
     const size_t n_keys = (size_t)set_off[n_sets], pkb = ecdsa_pk_bytes(pk_format), cb = (size_t)MUSIG_CACHE_BYTES * n_sets;
     const agg_sum_plan p = musig_agg_plan_sum(set_off, n_sets, agg_fanin(e));
-    if (!engine_workspace(e, ws_need({4 * n_sets, cb, 64 * n_sets, pkb * n_keys}) + keyagg_ws(p, n_keys, n_sets))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n_sets); unsigned char* d_cache = w.take<unsigned char>(cb); unsigned char* d_agg = w.take<unsigned char>(64 * n_sets);
-    unsigned char* d_pk = w.take<unsigned char>(pkb * n_keys);
-    if (n_keys) HIPCHK(hipMemcpyAsync(d_pk, pubkeys, pkb * n_keys, hipMemcpyHostToDevice, e->stream));
-    if (!keyagg_run(e, e->stream, w, p, d_res, d_cache, agg_pks_out64 ? d_agg : nullptr, d_pk, pk_format, n_sets)) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n_sets, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(caches_out197, d_cache, cb, hipMemcpyDeviceToHost, e->stream));
-    if (agg_pks_out64) HIPCHK(hipMemcpyAsync(agg_pks_out64, d_agg, 64 * n_sets, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n_sets}, {nullptr, caches_out197, cb}, {nullptr, agg_pks_out64, 64 * n_sets}, {pubkeys, nullptr, pkb * n_keys}};
+    if (!stage_open(e, b, 0, keyagg_ws(p, n_keys, n_sets))) return 0;
+    ws_carver w{e->ws, stage_bytes(b)};
+    return stage_close(e, b, keyagg_run(e, e->stream, w, p, b[0].at<int32_t>(), b[1].at(), agg_pks_out64 ? b[2].at() : nullptr, b[3].at(), pk_format, n_sets));
 }
 
 // ---- the cache tweaks --------------------------------------------------------------------------------------------------------------------
@@ -259,21 +252,13 @@ extern "C" int secp256k1_musig_pubkey_tweak_add_batch(s2k_engine* e, int32_t* re
     if (pubkeys_out64) memset(pubkeys_out64, 0, 64 * n);
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    if (!engine_workspace(e, ws_need({4 * n, cb, 64 * n, 32 * n, n}))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n); unsigned char* d_cache = w.take<unsigned char>(cb); unsigned char* d_pk = w.take<unsigned char>(64 * n);
-    unsigned char* d_tw = w.take<unsigned char>(32 * n); unsigned char* d_xo = w.take<unsigned char>(n);
-    HIPCHK(hipMemcpyAsync(d_cache, caches_in197, cb, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(d_tw, tweaks32, 32 * n, hipMemcpyHostToDevice, e->stream));
-    if (xonly) HIPCHK(hipMemcpyAsync(d_xo, xonly, n, hipMemcpyHostToDevice, e->stream));
-    if (!secp256k1_musig_pubkey_tweak_add_batch_dev(e, nullptr, d_res, d_cache, pubkeys_out64 ? d_pk : nullptr, d_cache, d_tw, xonly ? d_xo : nullptr, n)) {
-        (void)hipStreamSynchronize(e->stream); memset(caches_out197, 0, cb); if (pubkeys_out64) memset(pubkeys_out64, 0, 64 * n); return 0;
+    // (the caches are tweaked in place on the device: one buffer, uploaded and downloaded)
+    stage_buf b[] = {{nullptr, results, 4 * n}, {caches_in197, caches_out197, cb}, {nullptr, pubkeys_out64, 64 * n}, {tweaks32, nullptr, 32 * n}, {xonly, nullptr, n}};
+    if (!stage_open(e, b)) return 0;
+    if (!secp256k1_musig_pubkey_tweak_add_batch_dev(e, nullptr, b[0].at<int32_t>(), b[1].at(), pubkeys_out64 ? b[2].at() : nullptr, b[1].at(), b[3].at(), b[4].opt(), n)) {
+        (void)stage_close(e, b, 0); memset(caches_out197, 0, cb); if (pubkeys_out64) memset(pubkeys_out64, 0, 64 * n); return 0;
     }
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(caches_out197, d_cache, cb, hipMemcpyDeviceToHost, e->stream));
-    if (pubkeys_out64) HIPCHK(hipMemcpyAsync(pubkeys_out64, d_pk, 64 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    return stage_close(e, b, 1);
 }
 
 // ---- nonce aggregation -------------------------------------------------------------------------------------------------------------------
@@ -333,15 +318,10 @@ extern "C" int secp256k1_musig_nonce_agg_batch(s2k_engine* e, int32_t* results, 
     stream_guard sg(e, e->stream);
     const size_t n = (size_t)nonce_off[n_sessions], nb = musig_nonce_bytes(nonce_format), ob = musig_nonce_bytes(out_format) * n_sessions;
     const agg_sum_plan p = musig_agg_plan_nonces(nonce_off, n_sessions, agg_fanin(e));
-    if (!engine_workspace(e, ws_need({4 * n_sessions, ob, nb * n}) + nonce_agg_ws(p, n))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n_sessions); unsigned char* d_out = w.take<unsigned char>(ob); unsigned char* d_nonce = w.take<unsigned char>(nb * n);
-    if (n) HIPCHK(hipMemcpyAsync(d_nonce, pubnonces, nb * n, hipMemcpyHostToDevice, e->stream));
-    if (!nonce_agg_run(e, e->stream, w, p, d_res, d_out, out_format, d_nonce, nonce_format, n_sessions)) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n_sessions, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(aggnonces_out, d_out, ob, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n_sessions}, {nullptr, aggnonces_out, ob}, {pubnonces, nullptr, nb * n}};
+    if (!stage_open(e, b, 0, nonce_agg_ws(p, n))) return 0;
+    ws_carver w{e->ws, stage_bytes(b)};
+    return stage_close(e, b, nonce_agg_run(e, e->stream, w, p, b[0].at<int32_t>(), b[1].at(), out_format, b[2].at(), nonce_format, n_sessions));
 }
 
 // ---- signature aggregation -----------------------------------------------------------------------------------------------------------------
@@ -391,15 +371,8 @@ extern "C" int secp256k1_musig_partial_sig_agg_batch(s2k_engine* e, int32_t* res
     HIPCHK(hipSetDevice(e->device));
     stream_guard sg(e, e->stream);
     const size_t n = (size_t)sig_off[n_sessions], sgb = musig_sig_bytes(sig_format), sb = (size_t)MUSIG_SESSION_BYTES * n_sessions;
-    if (!engine_workspace(e, ws_need({4 * n_sessions, 64 * n_sessions, sb, sgb * n, 8 * (n_sessions + 1)}))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n_sessions); unsigned char* d_out = w.take<unsigned char>(64 * n_sessions); unsigned char* d_sess = w.take<unsigned char>(sb);
-    unsigned char* d_sig = w.take<unsigned char>(sgb * n);
-    HIPCHK(hipMemcpyAsync(d_sess, sessions133, sb, hipMemcpyHostToDevice, e->stream));
-    if (n) HIPCHK(hipMemcpyAsync(d_sig, partial_sigs, sgb * n, hipMemcpyHostToDevice, e->stream));
-    if (!sig_agg_run(e, e->stream, w, d_res, d_out, d_sess, d_sig, sig_format, sig_off, n_sessions)) { (void)hipStreamSynchronize(e->stream); return 0; }
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n_sessions, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(sigs64_out, d_out, 64 * n_sessions, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n_sessions}, {nullptr, sigs64_out, 64 * n_sessions}, {sessions133, nullptr, sb}, {partial_sigs, nullptr, sgb * n}};
+    if (!stage_open(e, b, 0, 8 * (n_sessions + 1))) return 0;      // (the runner's offsets)
+    ws_carver w{e->ws, stage_bytes(b)};
+    return stage_close(e, b, sig_agg_run(e, e->stream, w, b[0].at<int32_t>(), b[1].at(), b[2].at(), b[3].at(), sig_format, sig_off, n_sessions));
 }

@@ -1,5 +1,4 @@
-#include "engine_internal.h"
-#include "schnorr_all.h"
+#include "engine_verdict.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // one verdict for n BIP-340 signatures (schnorr_all.h): one (2n+1)-term MSM behind a hash tree
@@ -10,13 +9,6 @@ k_sa_items(unsigned char* pts, u32* nodes, unsigned char* sc, u32* flags, sa_mid
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (!sa_item(pts + 128 * i, nodes + 8 * i, sc + 64 * i + 32, mid, bip340, sigs + 64 * i, msgs + msglen * i, msglen, pks + (pk_format ? 64 : 32) * i, pk_format)) flags[0] = 1u;
-}
-__global__ void __launch_bounds__(256)
-k_sa_node(u32* out, const u32* __restrict__ in, sa_midstates mid, size_t cnt_in, size_t cnt_out) {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= cnt_out) return;
-    const size_t left = cnt_in - SA_FANIN * j;
-    sa_node(out + 8 * j, mid, in + 8 * SA_FANIN * j, left < SA_FANIN ? (u32)left : SA_FANIN);
 }
 __global__ void k_sa_seed(u32* seed8, unsigned char* seed32_out, sa_midstates mid, const u32* root8, u64 n, u64 msglen) {
     if (threadIdx.x || blockIdx.x) return;
@@ -39,10 +31,6 @@ k_sa_sum(unsigned char* out, const unsigned char* __restrict__ in, size_t cnt_in
     const size_t left = cnt_in - SA_FANIN * j;
     sa_sum_node(out + 32 * j, in + 32 * SA_FANIN * j, left < SA_FANIN ? (u32)left : SA_FANIN, negate);
 }
-__global__ void k_sa_final(int32_t* verdict, const u32* flags, const u32* res28) {
-    if (threadIdx.x || blockIdx.x) return;
-    *verdict = (flags[0] == 0u) && (res28[27] != 0u);
-}
 // n >= 1
 static size_t sa_ws_bytes(const s2k_engine* e, size_t n) {
     const size_t nt = 2 * n + 1;
@@ -51,13 +39,10 @@ static size_t sa_ws_bytes(const s2k_engine* e, size_t n) {
 static const sa_midstates& sa_mid() { static const sa_midstates m = [] { sa_midstates v; sa_make_midstates(v); return v; }(); return m; }
 // device pointers in, verdict to d_verdict[0] and (when asked for) the seed to d_seed_out; n >= 1, 2n + 1 <= msm_max_terms.
 // Timing: ev[0] .. ev_sa[0] the lift, the item digests and the challenges; .. ev_sa[1] the tree and the seed; .. ev[2] the coefficients, the
-// products and the scalar sum; ev[2] .. ev[3] the MSM; ev[1] the end.  msm_launch records ev[2] / ev[3] around its own dominant kernel:
-// for the duration of that call the two slots hold stand-ins (the engine's lock is held), so that s2k_engine_last_ms(1) is the whole MSM.
+// products and the scalar sum; ev[2] .. ev[3] the MSM; ev[1] the end (verdict_tail).
 static int sa_launch(s2k_engine* e, hipStream_t st, ws_carver& c, int32_t* d_verdict, unsigned char* d_seed_out, const unsigned char* d_sig, const unsigned char* d_msg,
                      size_t msglen, const unsigned char* d_pk, int pk_format, size_t n) {
-    for (int k = 0; k < 4; k++) if (!e->ev_sa[k]) HIPCHK(hipEventCreate(&e->ev_sa[k]));
-    size_t counts[SA_MAX_LEVELS];
-    const int levels = sa_level_plan(counts, n);
+    if (!verdict_events(e->ev_sa)) return 0;
     unsigned char* d_pts = c.take<unsigned char>(128 * n + 64); unsigned char* d_sc = c.take<unsigned char>(64 * n + 64);
     u32* d_nodes = c.take<u32>(sa_node_count(n) * 8 + 16); unsigned char* d_t = c.take<unsigned char>(32 * n + 64);
     unsigned char* d_sums = c.take<unsigned char>(sa_sum_count(n) * 32 + 64); u32* d_seed = c.take<u32>(16); u32* d_flags = c.take<u32>(16);
@@ -68,13 +53,8 @@ static int sa_launch(s2k_engine* e, hipStream_t st, ws_carver& c, int32_t* d_ver
     const unsigned bn = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_sa_items, dim3(bn), dim3(256), 0, st, d_pts, d_nodes, d_sc, d_flags, mid, e->bip340, d_sig, d_msg, msglen, d_pk, pk_format, n);
     HIPCHK(hipEventRecord(e->ev_sa[0], st));
-    u32* level = d_nodes;
-    for (int k = 0; k + 1 < levels; k++) {
-        u32* next = level + 8 * counts[k];
-        hipLaunchKernelGGL(k_sa_node, dim3((unsigned)((counts[k + 1] + 255) / 256)), dim3(256), 0, st, next, (const u32*)level, mid, counts[k], counts[k + 1]);
-        level = next;
-    }
-    hipLaunchKernelGGL(k_sa_seed, dim3(1), dim3(64), 0, st, d_seed, d_seed_out, mid, (const u32*)level, (u64)n, (u64)msglen);
+    const u32* root = verdict_tree(st, d_nodes, mid, n);
+    hipLaunchKernelGGL(k_sa_seed, dim3(1), dim3(64), 0, st, d_seed, d_seed_out, mid, root, (u64)n, (u64)msglen);
     HIPCHK(hipEventRecord(e->ev_sa[1], st));
     hipLaunchKernelGGL(k_sa_scalars, dim3(bn), dim3(256), 0, st, d_sc, d_t, mid, (const u32*)d_seed, d_sig, n);
     // -(sum a_i s_i): the terms, then one level of partial sums per pass; the pass that leaves one value negates it (n = 1: the only pass)
@@ -86,19 +66,8 @@ static int sa_launch(s2k_engine* e, hipStream_t st, ws_carver& c, int32_t* d_ver
         in = out; out += 32 * cnt_out; cnt = cnt_out;
     } while (cnt > 1);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[2], st));
-    u32* res28 = nullptr;
     // the MSM's points are R_0, P_0, R_1, P_1, ... with scalars a_0, a_0 e_0, a_1, a_1 e_1, ...; the generator term carries -(sum a_i s_i)
-    hipEvent_t const keep2 = e->ev[2], keep3 = e->ev[3];
-    e->ev[2] = e->ev_sa[2]; e->ev[3] = e->ev_sa[3];
-    const int ok = msm_launch(e, st, c, &res28, in, d_sc, d_pts, nullptr, 2 * n);
-    e->ev[2] = keep2; e->ev[3] = keep3;
-    if (!ok) return 0;
-    HIPCHK(hipEventRecord(e->ev[3], st));
-    hipLaunchKernelGGL(k_sa_final, dim3(1), dim3(64), 0, st, d_verdict, (const u32*)d_flags, (const u32*)res28);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    return verdict_tail(e, st, c, e->ev_sa, d_verdict, d_flags, in, d_sc, d_pts, nullptr, 2 * n);
 }
 // more than msm_max_terms terms (2n + 1 of them), or more message bytes than a call indexes
 static int sa_size_ok(const char* who, const s2k_engine* e, size_t msglen, size_t n) {
@@ -116,12 +85,7 @@ extern "C" int secp256k1_schnorrsig_verify_all_dev(s2k_engine* e, void* stream, 
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
     stream_guard sg(e, st);
-    if (n == 0) {                                              // nothing to refuse: verdict 1, the seed 32 zero bytes
-        launch_set_word(st, (u32*)verdict_dev, 1u);
-        HIPCHK(hipGetLastError());
-        if (seed32_out_dev) HIPCHK(hipMemsetAsync(seed32_out_dev, 0, 32, st));
-        return 1;
-    }
+    if (n == 0) return verdict_reply(st, verdict_dev, seed32_out_dev, 1u);      // nothing to refuse
     if (!engine_workspace(e, sa_ws_bytes(e, n))) return 0;
     ws_carver c{e->ws, 0};
     return sa_launch(e, st, c, verdict_dev, seed32_out_dev, sigs, msgs, msglen, pubkeys, pk_format, n);
@@ -140,42 +104,16 @@ extern "C" int secp256k1_schnorrsig_verify_all(s2k_engine* e, int32_t* verdict, 
     if (seed32_out) memset(seed32_out, 0, 32);
     if (n == 0) { *verdict = 1; return 1; }
     HIPCHK(hipSetDevice(e->device));
-    const size_t pkb = pk_format ? 64 : 32, front = sa_ws_bytes(e, n);
-    if (!engine_workspace(e, front + ws_need({64 * n + 64, msglen * n + 64, pkb * n + 64, 4 * n + 64, 64, 16}))) return 0;
-    ws_carver c0{e->ws, front};
-    unsigned char* d_sig = c0.take<unsigned char>(64 * n + 64); unsigned char* d_msg = c0.take<unsigned char>(msglen * n + 64);
-    unsigned char* d_pk = c0.take<unsigned char>(pkb * n + 64); int32_t* d_res = c0.take<int32_t>(n + 16);
-    unsigned char* d_seed = c0.take<unsigned char>(64); int32_t* d_verdict = c0.take<int32_t>(4);
-    hipStream_t st = e->stream;
-    {
-        stream_guard sg(e, st);
-        HIPCHK(hipMemcpyAsync(d_sig, sigs, 64 * n, hipMemcpyHostToDevice, st));
-        if (msglen) HIPCHK(hipMemcpyAsync(d_msg, msgs, msglen * n, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_pk, pubkeys, pkb * n, hipMemcpyHostToDevice, st));
-        ws_carver c{e->ws, 0};
-        if (!sa_launch(e, st, c, d_verdict, seed32_out ? d_seed : nullptr, d_sig, d_msg, msglen, d_pk, pk_format, n)) return 0;
-        HIPCHK(hipMemcpyAsync(verdict, d_verdict, 4, hipMemcpyDeviceToHost, st));
-        if (seed32_out) HIPCHK(hipMemcpyAsync(seed32_out, d_seed, 32, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    if (!results) return 1;
-    if (*verdict) { for (size_t i = 0; i < n; i++) results[i] = 1; return 1; }
-    // which items: the per-item verifier (it uses the per-lane tables, not the workspace: the uploaded buffers are still there)
-    if (!secp256k1_schnorrsig_verify_batch_dev(e, nullptr, d_res, d_sig, d_msg, msglen, d_pk, pk_format, n)) return 0;
-    HIPCHK(hipMemcpyAsync(results, d_res, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
+    const size_t pkb = pk_format ? 64 : 32;
+    const stage_buf in[] = {{sigs, nullptr, 64 * n, 64}, {msgs, nullptr, msglen * n, 64}, {pubkeys, nullptr, pkb * n, 64}};
+    return verdict_host(e, in, sa_ws_bytes(e, n), verdict, results, seed32_out, n,
+        [&](hipStream_t st, ws_carver& c, int32_t* d_verdict, unsigned char* d_seed, const stage_buf* b) {
+            return sa_launch(e, st, c, d_verdict, d_seed, b[0].at(), b[1].at(), msglen, b[2].at(), pk_format, n); },
+        // which items: the per-item verifier (it uses the per-lane tables, not the workspace: the uploaded buffers are still there)
+        [&](int32_t* d_res, const stage_buf* b) { return secp256k1_schnorrsig_verify_batch_dev(e, nullptr, d_res, b[0].at(), b[1].at(), msglen, b[2].at(), pk_format, n); });
 }
 // The phases of the most recent verify_all call of this engine, in ms, once its work is complete (s2k_engine_sync): [0] lift, item digests
 // and challenges, [1] hash tree and seed, [2] coefficients, products and the scalar sum, [3] the MSM.  -1 where no such call has run.
 extern "C" int s2k_schnorr_all_last_split_ms(s2k_engine* e, float* out4) {
-    if (!e) return s2k_fail("s2k_schnorr_all_last_split_ms", "null engine");
-    if (!out4) return s2k_fail_arg("s2k_schnorr_all_last_split_ms", "illegal argument");
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    HIPCHK(hipSetDevice(e->device));
-    for (int k = 0; k < 4; k++) out4[k] = -1.0f;
-    if (!e->ev_sa[0] || !e->ev_sa[1]) return 1;
-    hipEvent_t const b[5] = {e->ev[0], e->ev_sa[0], e->ev_sa[1], e->ev[2], e->ev[3]};
-    for (int k = 0; k < 4; k++) if (hipEventElapsedTime(&out4[k], b[k], b[k + 1]) != hipSuccess) { (void)hipGetLastError(); out4[k] = -1.0f; }
-    return 1;
+    return verdict_split_ms("s2k_schnorr_all_last_split_ms", e, &s2k_engine::ev_sa, out4);
 }

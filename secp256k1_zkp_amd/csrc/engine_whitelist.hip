@@ -1,4 +1,4 @@
-#include "engine_internal.h"
+#include "engine_lanes.h"
 #include "whitelist.h"
 
 // ------------------------------------------------------------------------------------------------------------
@@ -134,21 +134,12 @@ extern "C" int secp256k1_whitelist_verify_batch(s2k_engine* e, int32_t* results,
     HIPCHK(hipSetDevice(e->device));
     // the items' bytes [sig_off[0], sig_off[n]) go to HBM as they are, with offsets relative to their start; every list is uploaded once
     const size_t sig_lo = (size_t)sig_off[0], sig_bytes = (size_t)(sig_off[n] - sig_off[0]), key_bytes = 64 * (size_t)list_off[n_lists];
-    const size_t front = ws_need({4 * n, sig_bytes + 64, key_bytes + 64, key_bytes + 64, 64 * n});
     hipStream_t st = e->stream;
     stream_guard sg(e, st);
-    if (!engine_workspace(e, front + wl_ws_bytes(n, n_lists, wl_pairs(sig_off, list_off, list_of, n)))) return 0;      // (sized once: growing the workspace moves it)
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n); unsigned char* d_sig = w.take<unsigned char>(sig_bytes + 64); unsigned char* d_on = w.take<unsigned char>(key_bytes + 64);
-    unsigned char* d_off = w.take<unsigned char>(key_bytes + 64); unsigned char* d_sub = w.take<unsigned char>(64 * n);
+    stage_buf b[] = {{nullptr, results, 4 * n}, {sigs + sig_lo, nullptr, sig_bytes, 64}, {online64, nullptr, key_bytes, 64}, {offline64, nullptr, key_bytes, 64}, {sub64, nullptr, 64 * n}};
+    if (!stage_open(e, b, 0, wl_ws_bytes(n, n_lists, wl_pairs(sig_off, list_off, list_of, n)))) return 0;
     std::vector<uint64_t> rel(n + 1);
     for (size_t i = 0; i <= n; i++) rel[i] = sig_off[i] - sig_lo;
-    if (sig_bytes) HIPCHK(hipMemcpyAsync(d_sig, sigs + sig_lo, sig_bytes, hipMemcpyHostToDevice, st));
-    if (key_bytes) { HIPCHK(hipMemcpyAsync(d_on, online64, key_bytes, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(d_off, offline64, key_bytes, hipMemcpyHostToDevice, st)); }
-    HIPCHK(hipMemcpyAsync(d_sub, sub64, 64 * n, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_res, 0, sizeof(int32_t) * n, st));
-    if (!wl_impl(e, st, front, d_res, d_sig, rel.data(), d_on, d_off, list_off, n_lists, list_of, d_sub, n)) { (void)hipStreamSynchronize(st); return 0; }
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
+    HIPCHK(hipMemsetAsync(b[0].dev, 0, sizeof(int32_t) * n, st));
+    return stage_close(e, b, wl_impl(e, st, stage_bytes(b), b[0].at<int32_t>(), b[1].at(), rel.data(), b[2].at(), b[3].at(), list_off, n_lists, list_of, b[4].at(), n));
 }
