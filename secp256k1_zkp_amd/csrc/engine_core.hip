@@ -158,6 +158,11 @@ k_gen_xmul(u32* __restrict__ xmul, const unsigned char* __restrict__ gen64, cons
     ge a; ge_set_gej(a, R);
     if (live) { u32 w[8]; fe_to_words(w, a.x); for (int i = 0; i < 8; i++) xmul[8 * tt + i] = w[i]; }
 }
+// the ring bases and their 2^64 multiples as Jacobian records (rp_gen_chain: the records rp_pp_bases writes per proof): one lane per exponent
+__global__ void k_gen_chain(u32* __restrict__ chain, const unsigned char* __restrict__ gen64) {
+    const u32 ex = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ex < RP_XMUL_EXPS) rp_gen_chain(chain + (size_t)ex * RP_CHAIN_RECS * RP_GEJ_WORDS, gen64, (int)ex);
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // batch double multiplication  r = na*A + ng*G    (secp256k1_ecmult, src/ecmult.h:47)
@@ -227,8 +232,8 @@ static s2k_dev_pool* pool_acquire(int device) {
     std::lock_guard<std::mutex> g(g_pools_mu);
     for (auto* p : g_pools) if (p->device == device) { p->refs++; return p; }
     s2k_dev_pool* p = new s2k_dev_pool();
-    p->device = device; p->refs = 1; p->gtab = nullptr; p->ev_gtab = nullptr; p->gtab_state = 0; p->gen_keys = nullptr;
-    for (int i = 0; i < RP_GEN_SLOTS; i++) { auto& g2 = p->gen[i]; g2.tab = nullptr; g2.xmul = nullptr; g2.valid = 0; g2.stamp = 0; g2.pinned = 0; g2.ev_ready = nullptr; g2.done = 0; }
+    p->device = device; p->refs = 1; p->gtab = nullptr; p->ev_gtab = nullptr; p->gtab_state = 0; p->gen_keys = nullptr; p->gen_chain = nullptr;
+    for (int i = 0; i < RP_GEN_SLOTS; i++) { auto& g2 = p->gen[i]; g2.tab = nullptr; g2.xmul = nullptr; g2.valid = 0; g2.ysq = 0; g2.stamp = 0; g2.pinned = 0; g2.ev_ready = nullptr; g2.done = 0; }
     p->gen_slots = 2; p->gen_clock = 0; p->gen_min = size_t(1) << 16; p->gen_h = 1;
     p->gtab_bits = S2K_GTAB_BITS;
     if (const char* gb = getenv("S2K_GTAB_BITS")) { const int v = atoi(gb); if (v >= 20 && v <= S2K_GTAB_MAX_BITS && gtab_bits_ok((u32)v)) p->gtab_bits = (u32)v; }
@@ -243,6 +248,7 @@ static s2k_dev_pool* pool_acquire(int device) {
     ok = ok && hipEventCreate(&p->ev_build[0]) == hipSuccess && hipEventCreate(&p->ev_build[1]) == hipSuccess;
     for (int i = 0; ok && i < RP_GEN_SLOTS; i++) ok = hipEventCreateWithFlags(&p->gen[i].ev_ready, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipMalloc((void**)&p->gen_keys, 64 * RP_GEN_SLOTS) == hipSuccess && hipMemset(p->gen_keys, 0, 64 * RP_GEN_SLOTS) == hipSuccess;
+    ok = ok && hipMalloc((void**)&p->gen_chain, sizeof(u32) * RP_CHAIN_WORDS * RP_GEN_SLOTS) == hipSuccess && hipMemset(p->gen_chain, 0, sizeof(u32) * RP_CHAIN_WORDS * RP_GEN_SLOTS) == hipSuccess;
     if (!ok) {
         s2k_fail("s2k_engine_create", "cannot create the device's table pool");
         (void)hipGetLastError();
@@ -250,6 +256,7 @@ static s2k_dev_pool* pool_acquire(int device) {
         for (int i = 0; i < 2; i++) if (p->ev_build[i]) hipEventDestroy(p->ev_build[i]);
         for (int i = 0; i < RP_GEN_SLOTS; i++) if (p->gen[i].ev_ready) hipEventDestroy(p->gen[i].ev_ready);
         if (p->gen_keys) hipFree(p->gen_keys);
+        if (p->gen_chain) hipFree(p->gen_chain);
         delete p; return nullptr;
     }
     g_pools.push_back(p);
@@ -263,6 +270,7 @@ static void pool_release(s2k_dev_pool* p) {
     g_pools.erase(std::remove(g_pools.begin(), g_pools.end(), p), g_pools.end());
     pool_free_tables(p);
     if (p->gen_keys) hipFree(p->gen_keys);
+    if (p->gen_chain) hipFree(p->gen_chain);
     if (p->ev_gtab) hipEventDestroy(p->ev_gtab);
     for (int i = 0; i < 2; i++) if (p->ev_build[i]) hipEventDestroy(p->ev_build[i]);
     for (int i = 0; i < RP_GEN_SLOTS; i++) if (p->gen[i].ev_ready) hipEventDestroy(p->gen[i].ev_ready);
@@ -306,7 +314,7 @@ const u32* engine_gtab(s2k_engine* e, hipStream_t st) {
 // The cache as the kernels of one launch see it; `st` / `sp`: the streams that will read the tables (made to wait for builds still in flight)
 rp_gen_dev gen_dev_view(s2k_engine* e, hipStream_t st, hipStream_t sp) {
     s2k_dev_pool* p = e->pool;
-    rp_gen_dev gc; gc.keys = p->gen_keys; gc.valid = 0; gc.any = 0;
+    rp_gen_dev gc; gc.keys = p->gen_keys; gc.valid = 0; gc.any = 0; gc.chain = p->gen_chain; gc.ysq = 0;
     for (int i = 0; i < RP_GEN_SLOTS; i++) {
         auto& g = p->gen[i];
         int v = i < p->gen_slots && g.valid;
@@ -318,7 +326,7 @@ rp_gen_dev gen_dev_view(s2k_engine* e, hipStream_t st, hipStream_t sp) {
             }
         }
         gc.tab[i] = v ? g.tab : nullptr; gc.xmul[i] = v ? g.xmul : nullptr;
-        if (v) { gc.valid |= 1u << i; gc.any = (u32)i; }
+        if (v) { gc.valid |= 1u << i; gc.any = (u32)i; gc.ysq |= (u32)g.ysq << i; }
     }
     return gc;
 }
@@ -377,6 +385,10 @@ int gen_cache_build(s2k_engine* e, hipStream_t st, const unsigned char* key, int
     hipLaunchKernelGGL(k_gen_base, dim3(1), dim3(64), 0, st, g.tab, p->gen_keys + 64 * slot, p->gtab_bits);
     if (!launch_table_build(st, g.tab, p->gtab_bits, 1)) { (void)hipGetLastError(); return -1; }
     hipLaunchKernelGGL(k_gen_xmul, dim3((RP_XMUL_EXPS * RP_MAX_RINGS * 3 + 255) / 256), dim3(256), 0, st, g.xmul, p->gen_keys + 64 * slot, gtab, e->ptab);
+    // what the prologue would otherwise work out again for every proof of this generator: the ring-base chain per exponent (its region
+    // of gen_chain is rewritten behind the same reader events as the table) and whether y is a square (a host-side square root, once)
+    hipLaunchKernelGGL(k_gen_chain, dim3(1), dim3(64), 0, st, p->gen_chain + (size_t)slot * RP_CHAIN_WORDS, p->gen_keys + 64 * slot);
+    g.ysq = rp_gen_y_is_square(key);
     if (hipGetLastError() != hipSuccess || hipEventRecord(g.ev_ready, st) != hipSuccess) { (void)hipGetLastError(); return -1; }
     g.valid = 1; g.done = 0; g.pinned = pinned; g.stamp = ++p->gen_clock;
     return slot;

@@ -236,9 +236,12 @@ struct s2k_dev_pool {
     // readers: the engines whose kernels may still read this slot's tables (each records its ev_gen_read[slot] behind the last kernel of
     // every call that took the slot into its view, pool mutex held from the view to the record): a build that REUSES the slot's memory makes
     // its stream wait for exactly those events -- no host wait, no device-wide synchronisation (round 6).
-    struct gen_slot { unsigned char key[64]; u32* tab; u32* xmul; unsigned long long stamp; int valid; int pinned; hipEvent_t ev_ready; int done; std::vector<s2k_engine*> readers; } gen[RP_GEN_SLOTS];
+    // What the prologue of a proof needs of its generator alone is kept per slot as well, filled by the build: gen_chain (device, the ring
+    // bases and their 2^64 multiples per exponent, rp_gen_chain) and ysq (whether the generator's y is a square).
+    struct gen_slot { unsigned char key[64]; u32* tab; u32* xmul; int ysq; unsigned long long stamp; int valid; int pinned; hipEvent_t ev_ready; int done; std::vector<s2k_engine*> readers; } gen[RP_GEN_SLOTS];
     int gen_slots; unsigned long long gen_clock; size_t gen_min; int gen_h;
     unsigned char* gen_keys;   // device, [RP_GEN_SLOTS][64]
+    u32* gen_chain;            // device, [RP_GEN_SLOTS][RP_CHAIN_WORDS]
     std::vector<std::pair<std::array<unsigned char, 64>, size_t>> gen_seen;
 };
 

@@ -15,10 +15,12 @@ k_rp_header(rp_ws ws, uint64_t* min_value, uint64_t* max_value, const unsigned c
     // which cached generator table (if any) serves this proof (a generator without one is reported by k_rp_final, for proofs that verified)
     ws.rec[p].gslot = rp_gen_lookup(gc, gens64 + 64 * p);
 }
-// three waves per 64 proofs: wave 0 commitment + min_value*H, wave 1 generator flag + message hash, wave 2 ring bases
+// three waves per 64 proofs: wave 0 commitment + min_value*H, wave 1 generator flag + message hash, wave 2 ring bases.
+// A proof whose generator has a cached table (gslot, set by k_rp_header) finds both per-generator parts in its slot: the flag comes from
+// gen_ysq and wave 2 writes nothing -- only a ring the shared form hands back needs bases, and gets them from the slot's chain (k_rp_handback_bases).
 __global__ void __launch_bounds__(192)
 k_rp_prologue(rp_ws ws, const uint64_t* min_value, const unsigned char* commits33, const unsigned char* proofs,
-              const uint64_t* proof_off, const unsigned char* extra, const uint64_t* extra_off, const unsigned char* gens64, size_t n) {
+              const uint64_t* proof_off, const unsigned char* extra, const uint64_t* extra_off, const unsigned char* gens64, u32 gen_valid, u32 gen_ysq, size_t n) {
     // few, latency-bound waves that share the SIMDs with the throughput-bound lift kernel: ask the arbiter to issue them first
     __builtin_amdgcn_s_setprio(3);
     const u32 role = threadIdx.x >> 6;
@@ -26,12 +28,13 @@ k_rp_prologue(rp_ws ws, const uint64_t* min_value, const unsigned char* commits3
     int commit_ok = 0;
     if (p < n) {
         rp_rec& rec = ws.rec[p];
+        const int served = rp_gen_served(gen_valid, rec.gslot);
         if (role == 0) commit_ok = rp_pp_commit(rec, min_value[p], commits33 + 33 * p, gens64 + 64 * p);
         else if (role == 1) {
             const unsigned char* ex = nullptr; uint64_t exlen = 0;
             if (extra && extra_off) { ex = extra + extra_off[p]; exlen = extra_off[p + 1] - extra_off[p]; if (exlen == 0) ex = nullptr; }
-            rp_pp_hash(rec, commits33 + 33 * p, proofs + proof_off[p], ex, exlen, gens64 + 64 * p);
-        } else rp_pp_bases(rec, ws.bases + p * RP_MAX_RINGS * RP_GEJ_WORDS, gens64 + 64 * p, ws.dbases + p * RP_MAX_RINGS * RP_GEJ_WORDS);
+            rp_pp_hash(rec, commits33 + 33 * p, proofs + proof_off[p], ex, exlen, gens64 + 64 * p, served ? (int)((gen_ysq >> rec.gslot) & 1u) : -1);
+        } else if (!served) rp_pp_bases(rec, ws.bases + p * RP_MAX_RINGS * RP_GEJ_WORDS, gens64 + 64 * p, ws.dbases + p * RP_MAX_RINGS * RP_GEJ_WORDS);
     }
     __syncthreads();
     if (p < n && role == 0 && (ws.rec[p].hdr & 1u) && commit_ok) ws.rec[p].ok = 1;      // (a commitment encoding that does not parse: never valid)
@@ -71,8 +74,7 @@ k_rp_sum(rp_ws ws, u32 gen_valid, size_t n) {
         const rp_rec& rec = ws.rec[p];
         if (rec.ok) {
             rings = rec.rings;
-            const int fast = gen_valid && rec.gslot < RP_GEN_SLOTS && ((gen_valid >> rec.gslot) & 1u);
-            if (fast) cF = (rings + S2K_RP_K - 1) / S2K_RP_K; else cG = rings;
+            if (rp_gen_served(gen_valid, rec.gslot)) cF = (rings + S2K_RP_K - 1) / S2K_RP_K; else cG = rings;
         }
     }
     u32 pf = cF, pg = cG;                                    // inclusive prefix sums over the wavefront (the workgroup is one wavefront)
@@ -120,6 +122,23 @@ k_rp_rings_shared(rp_ws ws, const unsigned char* __restrict__ proofs, const uint
         const u32 base = atomicAdd(&ws.plan[1], cnt);
         for (u32 i = 0; i < cnt; i++) ws.mapG[base + i] = (u32)p | ((r0 + i) << 20);
         atomicAdd(&ws.plan[served == RP_SHARED_SUSPECT ? 2 : 3], cnt);      // diagnostics: s2k_engine_rp_handback
+    }
+}
+// Between the two: the rings the shared form handed back belong to proofs of a cached generator, for which k_rp_prologue wrote no bases.
+// Their base and its 2^64 multiple come from the slot's chain -- the same words -- into the proof's own records, one ring per lane (a
+// few resident blocks stride over mapG; none but hand-backs of adversarial input are ever copied).  A kernel of its own rather than a
+// lane-dependent pointer inside k_rp_rings: that kernel sits at its register limit, and the choice cost it 8 to 16 more bytes of scratch.
+__global__ void __launch_bounds__(256)
+k_rp_handback_bases(rp_ws ws, const u32* __restrict__ chain, u32 gen_valid) {
+    const u32 nG = ws.plan[1];
+    for (u32 t = blockIdx.x * blockDim.x + threadIdx.x; t < nG; t += gridDim.x * blockDim.x) {
+        const u32 item = ws.mapG[t];
+        const size_t p = item & 0xFFFFFu; const u32 ring = item >> 20;
+        const rp_rec& rec = ws.rec[p];
+        if (!rp_gen_served(gen_valid, rec.gslot)) continue;
+        const u32* src = rp_gen_chain_rec(chain, rec.gslot, rec.hdr, ring);
+        u32* const b = ws.bases + (p * RP_MAX_RINGS + ring) * RP_GEJ_WORDS; u32* const d = ws.dbases + (p * RP_MAX_RINGS + ring) * RP_GEJ_WORDS;
+        for (int i = 0; i < RP_GEJ_WORDS; i++) { b[i] = src[i]; d[i] = src[RP_MAX_RINGS * RP_GEJ_WORDS + i]; }
     }
 }
 __global__ void __launch_bounds__(256, S2K_RINGS_WAVES)
@@ -254,7 +273,7 @@ int engine_rp_slots(s2k_engine* e, size_t nw) {
 }
 // Launches the five stages, chunk by chunk (RP_CHUNK proofs), as a two-deep pipeline:
 //   side streams   : header -> { prologue (1 lane/proof, latency bound) || lift (1 lane/ring, lowest priority) } -> key sum
-//   caller's stream: rings (the 98 %) -> final [-> rewind]
+//   caller's stream: rings (the 98 %; shared form -> bases of its hand-backs -> general form) -> final [-> rewind]
 // Chunk i+1's side-stream stage runs while chunk i's rings kernel owns the machine; the scratch records alternate between two sets and a
 // set is reused only after the rings/final that read it.  By default the side-stream stage of a call also waits for everything the
 // caller had queued on `st` before the call (its inputs may still be in the making); with S2K_OPT_RP_INPUTS_READY the caller
@@ -294,7 +313,7 @@ static int rp_launch(s2k_engine* e, hipStream_t st, int32_t* results, uint64_t* 
         hipLaunchKernelGGL(k_rp_lift, dim3(b256), dim3(256), 0, e->stream2, w, proofs, proof_off + p0, m);
         HIPCHK(hipEventRecord(e->ev_rp_join[slot], e->stream2));
         hipLaunchKernelGGL(k_rp_prologue, dim3(b64), dim3(192), 0, sp, w, min_value + p0, commits33 + 33 * p0, proofs, proof_off + p0, extra,
-                           extra_off ? extra_off + p0 : nullptr, gens64 + 64 * p0, m);
+                           extra_off ? extra_off + p0 : nullptr, gens64 + 64 * p0, gc.valid, gc.ysq, m);
         HIPCHK(hipStreamWaitEvent(sp, e->ev_rp_join[slot], 0));
         hipLaunchKernelGGL(k_rp_sum, dim3(b64), dim3(64), 0, sp, w, gc.valid, m);
         HIPCHK(hipEventRecord(e->ev_rp_pre[slot], sp));
@@ -311,8 +330,11 @@ static int rp_launch(s2k_engine* e, hipStream_t st, int32_t* results, uint64_t* 
         HIPCHK(hipStreamWaitEvent(st, e->ev_rp_pre[slot], 0));
         const unsigned rq = e->ring_seq & 31u;
         if (p0 == 0) { HIPCHK(hipEventRecord(e->ev[2], st)); HIPCHK(hipEventRecord(e->ev_ring[rq][0], st)); }
-        if (gc.valid) hipLaunchKernelGGL(k_rp_rings_shared, dim3((unsigned)((m * (RP_MAX_RINGS / S2K_RP_K) + 255) / 256)), dim3(256), 0, st, w, proofs, proof_off + p0, e->gtab, e->ptab,
-                                         rewind ? rewind->ev : (u32*)nullptr, gc, (u32)e->rp_debug);
+        if (gc.valid) {
+            hipLaunchKernelGGL(k_rp_rings_shared, dim3((unsigned)((m * (RP_MAX_RINGS / S2K_RP_K) + 255) / 256)), dim3(256), 0, st, w, proofs, proof_off + p0, e->gtab, e->ptab,
+                               rewind ? rewind->ev : (u32*)nullptr, gc, (u32)e->rp_debug);
+            hipLaunchKernelGGL(k_rp_handback_bases, dim3(std::min(b256, 64u)), dim3(256), 0, st, w, gc.chain, gc.valid);
+        }
         hipLaunchKernelGGL(k_rp_rings, dim3(b256), dim3(256), 0, st, w, proofs, proof_off + p0, e->gtab, e->ptab, rewind ? rewind->ev : (u32*)nullptr, e->rp_split);
         if (p0 == 0) { HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev_ring[rq][1], st)); e->ring_seq++; }
         hipLaunchKernelGGL(k_rp_final, dim3(b64), dim3(64), 0, st, w, results + p0, proofs, proof_off + p0, gens64 + 64 * p0,

@@ -42,7 +42,7 @@ struct rp_rec {
 
 struct rp_ws {           // device pointers into the engine workspace
     rp_rec* rec;         // [n]
-    u32* bases;          // [n][32][28]
+    u32* bases;          // [n][32][28]  ring bases of the proofs WITHOUT a cached generator (k_rp_prologue) and of handed-back rings (k_rp_handback_bases); dbases likewise
     u32* pub0;           // [n][32][28]
     u32* dbases;         // [n][32][28]  2^64 * B_i : the step of T = 2^64 * key from one ring position to the next (ecmult_lane_split)
     u32* tcur;           // [n][32][28]  2^64 * (current key of the ring)
@@ -166,10 +166,15 @@ S2K_HD int rp_pp_commit(rp_rec& rec, u64 min_value, const unsigned char* commit3
     gej_store28_h(rec.accj, acc);
     return valid;
 }
+S2K_HD int rp_gen_y_is_square(const unsigned char* gen64) {
+    ge g; rp_load_generator(g, gen64);
+    fe r; return fe_sqrt(r, g.y);
+}
 // B: m = SHA256( ser(commit) || ser(gen) || proof[0..off_hdr) || (sign_i || x_i)_{i<rings-1} || extra )   (:588-651)
 //    ser(point) = [ !is_square(y) ] || x   (rangeproof_serialize_point :53-59)
+// gsq: whether the generator's y is a square when the caller knows it (0 / 1: the generator cache keeps it per slot), -1 = find out here
 S2K_HD void rp_pp_hash(rp_rec& rec, const unsigned char* commit33, const unsigned char* proof, const unsigned char* extra, u64 extra_len,
-                       const unsigned char* gen64) {
+                       const unsigned char* gen64, int gsq = -1) {
     if (!(rec.hdr & 1u)) return;
     const u32 rings = rec.rings, off_hdr = rec.off_signs;
     ge g; rp_load_generator(g, gen64);
@@ -182,7 +187,7 @@ S2K_HD void rp_pp_hash(rp_rec& rec, const unsigned char* commit33, const unsigne
     const int cy_zero = fe_normalizes_to_zero(rhs);
     sha256_stream_put(h, (unsigned char)((commit33[0] & 1) && !cy_zero ? 1 : 0));
     fe_get_b32(buf, cx); sha256_stream_write(h, buf, 32);
-    fe r; const int gsq = fe_sqrt(r, g.y);
+    if (gsq < 0) { fe r; gsq = fe_sqrt(r, g.y); }
     sha256_stream_put(h, (unsigned char)(!gsq));
     fe_get_b32(buf, g.x); sha256_stream_write(h, buf, 32);
     sha256_stream_write(h, proof, off_hdr);
@@ -197,26 +202,41 @@ S2K_HD void rp_pp_hash(rp_rec& rec, const unsigned char* commit33, const unsigne
     for (int i = 0; i < 8; i++) rec.m[i] = s2k_load_be32(m + 4 * i);
 }
 // C: ring bases: base_0 = -(10^exp) H, base_{i+1} = 4 base_i   (pub_expand, rangeproof_impl.h:20-51)
-S2K_HD void rp_pp_bases(const rp_rec& rec, u32* bases /*[32][28]*/, const unsigned char* gen64, u32* dbases = nullptr /*[32][28]*/) {
-    if (!(rec.hdr & 1u)) return;
-    const u32 rings = rec.rings;
-    const int exp = (int)((rec.hdr >> 8) & 0xFFu) - 1;
+// base_0 = -(10^exp) gen, weakly normalised: where the chain of a (generator, exp) starts -- for one proof (rp_pp_bases) and for a
+// generator-cache slot (rp_gen_chain); both walk it with the same two lean doublings per record, so their records are the same words
+S2K_HD void rp_base_first(gej& base, const unsigned char* gen64, int exp) {
     ge g; rp_load_generator(g, gen64);
-    gej base; ge ng; ng.x = g.x; fe_neg(ng.y, g.y, 1); fe_norm_weak(ng.y);
+    ge ng; ng.x = g.x; fe_neg(ng.y, g.y, 1); fe_norm_weak(ng.y);
     gej_set_ge(base, ng);
     for (int e = 0; e < exp; e++) {          // multiplication by 10 = 8x + 2x
         gej t2, t8, s;
         gej_double(t2, base); gej_double(t8, t2); gej_double(s, t8);
         gej_add_var(base, s, t2);
     }
+    fe_norm_weak(base.x); fe_norm_weak(base.y);
+}
+S2K_HD void rp_pp_bases(const rp_rec& rec, u32* bases /*[32][28]*/, const unsigned char* gen64, u32* dbases = nullptr /*[32][28]*/) {
+    if (!(rec.hdr & 1u)) return;
+    const u32 rings = rec.rings;
+    gej base; rp_base_first(base, gen64, (int)((rec.hdr >> 8) & 0xFFu) - 1);
     // One chain: base_{i+1} = 4 base_i, and 2^64 * base_i is simply base_{i+32} -- the steps of the keys' 2^64-multiples (dbases) are
     // the continuation of the same chain, 2 * (rings + 31) doublings in all.
-    fe_norm_weak(base.x); fe_norm_weak(base.y);
     const u32 total = dbases ? rings + 32 : rings;
     for (u32 i = 0; i < total; i++) {
         if (i < rings) gej_store28_h(bases + RP_GEJ_WORDS * i, base);
         if (dbases && i >= 32) gej_store28_h(dbases + RP_GEJ_WORDS * (i - 32), base);
         if (i + 1 < total) { gej_double_lean(base, base); gej_double_lean(base, base); }
+    }
+}
+// The whole chain of one (generator, exponent index): RP_CHAIN_RECS records, record i = 4^i base_0 -- records 0..31 are the ring bases,
+// records 32..63 their 2^64 multiples (what rp_pp_bases writes as bases[i] and dbases[i - 32] for a proof of 32 rings; a shorter proof
+// gets a prefix of each half).  Depends on (generator, exp) alone: the generator cache builds it once per slot (k_gen_chain).
+#define RP_CHAIN_RECS (2 * RP_MAX_RINGS)
+S2K_HD void rp_gen_chain(u32* chain /*[RP_CHAIN_RECS][28]*/, const unsigned char* gen64, int exp) {
+    gej base; rp_base_first(base, gen64, exp);
+    for (u32 i = 0; i < RP_CHAIN_RECS; i++) {
+        gej_store28_h(chain + RP_GEJ_WORDS * i, base);
+        if (i + 1 < RP_CHAIN_RECS) { gej_double_lean(base, base); gej_double_lean(base, base); }
     }
 }
 S2K_HD void rp_prologue_points(rp_rec& rec, u32* bases /*[32][28]*/, u64 min_value, const unsigned char* commit33,
@@ -426,7 +446,11 @@ struct rp_gen_dev {                       // by value to the kernels: the cache 
     const unsigned char* keys;            // [RP_GEN_SLOTS][64] generator bytes
     u32 valid;                            // bit i: slot i holds a table
     u32 any;                              // index of some valid slot (idle lanes read its x-table)
+    const u32* chain;                     // [RP_GEN_SLOTS][RP_CHAIN_WORDS]: every slot's ring-base chains (rp_gen_chain), one allocation
+    u32 ysq;                              // bit i: the y of slot i's generator is a square (the flag byte of the message hash)
 };
+// a proof whose generator has a table in this launch's view of the cache (gslot: rp_gen_lookup, by k_rp_header)
+S2K_HD int rp_gen_served(u32 gen_valid, u32 gslot) { return gslot < RP_GEN_SLOTS && ((gen_valid >> gslot) & 1u); }
 // Generators that had no table, reported by the LAST stage (k_rp_final) for proofs that VERIFIED only -- an attacker cannot make the
 // engine spend 0.6 s and 21.5 GB on a table by sending junk proofs that merely name a generator (the first few distinct generators of
 // a call, with the number of valid proofs that carried them).  A slot is claimed by a 64-bit tag of the generator bytes (one
@@ -492,6 +516,12 @@ __device__ __forceinline__ void rp_gen_report_miss(rp_gen_mbox* mb, const unsign
 // scalar) ride along on a dummy point / dummy scalars so that the wavefront stays in lock step; their results are discarded.
 #define RP_XMUL_EXPS 19
 #define RP_XMUL_WORDS (RP_XMUL_EXPS * RP_MAX_RINGS * 3 * 8)       /* [exp][ring][j-1][8 canonical words, least significant first] */
+#define RP_CHAIN_WORDS (RP_XMUL_EXPS * RP_CHAIN_RECS * RP_GEJ_WORDS)  /* one slot: [exp][record][28], the exponent index of xmul */
+// the base record of `ring` for a proof with header word `hdr` served by `slot`; its 2^64 multiple lies RP_MAX_RINGS records further on
+S2K_HD const u32* rp_gen_chain_rec(const u32* chain, u32 slot, u32 hdr, u32 ring) {
+    const int exp = (int)((hdr >> 8) & 0xFFu) - 1;
+    return chain + (((size_t)slot * RP_XMUL_EXPS + (size_t)(exp < 0 ? 0 : exp)) * RP_CHAIN_RECS + ring) * RP_GEJ_WORDS;
+}
 S2K_HD void rp_ring_const(scalar& c, int exp, u32 ring) {         // 4^ring * 10^exp  (< 2^124)
     u64 scale = 1;
     for (int i = 0; i < exp; i++) scale *= 10;
