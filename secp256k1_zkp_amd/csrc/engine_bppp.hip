@@ -206,7 +206,6 @@ extern "C" int secp256k1_bppp_norm_product_verify_batch(s2k_engine* e, int32_t* 
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     const size_t per = std::max<size_t>(1, e->max_lanes / sh.n_terms);
-    stream_guard sg(e, e->stream);
     // the `_dev` form carves its launch groups from offset 0: the buffers lie behind
     stage_buf b[] = {{nullptr, results, 4 * n}, {proofs, nullptr, n * proof_len, 64}, {transcripts, nullptr, 104 * n}, {rho, nullptr, 32 * n}, {gens33, nullptr, 33 * n_gens},
                      {c_vec, nullptr, 32 * c_vec_len * n}, {commits33, nullptr, 33 * n}};
@@ -319,7 +318,6 @@ extern "C" int secp256k1_bppp_commit_batch(s2k_engine* e, unsigned char* commits
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     const size_t per = std::max<size_t>(1, e->max_lanes / (n_gens + 1));
-    stream_guard sg(e, e->stream);
     stage_buf b[] = {{nullptr, commits33, 33 * n}, {nullptr, results, 4 * n}, {gens33, nullptr, 33 * n_gens}, {n_vec, nullptr, 32 * g_len * n}, {l_vec, nullptr, 32 * h_len * n},
                      {c_vec, nullptr, 32 * h_len * n}, {mu, nullptr, 32 * n}};
     if (!stage_open(e, b, bpc_ws_bytes(std::min(n, per), n_gens))) return 0;

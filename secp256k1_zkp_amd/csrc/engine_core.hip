@@ -729,268 +729,216 @@ static s2k_engine* default_engine() {
     }
     return g_default_engine;
 }
+// ------------------------------------------------------------------------------------------------------------
+// single-item forms with the reference's argument lists.  A 0 from these means "invalid" only while s2k_last_status() is
+// S2K_STATUS_OK; an engine-level failure also returns 0 (never 1) and leaves S2K_STATUS_ENGINE_FAILURE for the caller's
+// CPU fallback (integration/secp256k1_amd_hook.c does exactly that).
+// ------------------------------------------------------------------------------------------------------------
+// What every such form does around its batch call, in two steps (a form with an early return of its own stands between them):
+// amd_args  clears the status, checks `ok`, zeroes `out` (when there is one), checks `ok_zeroed`: 0 with the ARG_CHECK failure set;
+// amd_call  takes the default engine, runs call(e, &res) and returns res -- or 0, with `out` zeroed again, when the call fails.
+static int amd_args(const char* who, bool ok, void* out = nullptr, size_t out_bytes = 0, bool ok_zeroed = true) {
+    s2k_clear_status();
+    if (!ok) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    if (out) memset(out, 0, out_bytes);
+    if (!ok_zeroed) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    return 1;
+}
+template <class Call>
+static int amd_call(void* out, size_t out_bytes, Call call) {
+    s2k_engine* e = default_engine();
+    if (!e) return 0;
+    int32_t res = 0;
+    if (!call(e, &res)) { if (out) memset(out, 0, out_bytes); return 0; }
+    return res;
+}
+template <class Call>
+static int amd_one(const char* who, bool ok, void* out, size_t out_bytes, bool ok_zeroed, Call call) {
+    return amd_args(who, ok, out, out_bytes, ok_zeroed) ? amd_call(out, out_bytes, call) : 0;
+}
+template <class Call>
+static int amd_one(const char* who, bool ok, Call call) { return amd_one(who, ok, nullptr, 0, true, call); }
+
 // include/secp256k1_rangeproof.h:70-80
 extern "C" int secp256k1_rangeproof_verify_amd(const void* ctx, uint64_t* min_value, uint64_t* max_value, const void* commit,
                                                const unsigned char* proof, size_t plen, const unsigned char* extra_commit,
                                                size_t extra_commit_len, const void* gen) {
     (void)ctx;
-    s2k_clear_status();
-    if (!min_value || !max_value || !commit || !proof || !gen || (!extra_commit && extra_commit_len)) return s2k_fail_arg("secp256k1_rangeproof_verify_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0; uint64_t off[2] = {0, plen}, eoff[2] = {0, extra_commit_len};
-    if (!secp256k1_rangeproof_verify_batch(e, &res, min_value, max_value, (const unsigned char*)commit, proof, off,
-                                           extra_commit_len ? extra_commit : nullptr, extra_commit_len ? eoff : nullptr, (const unsigned char*)gen, 1)) return 0;
-    return res;
+    return amd_one("secp256k1_rangeproof_verify_amd", min_value && max_value && commit && proof && gen && (extra_commit || !extra_commit_len), [&](s2k_engine* e, int32_t* res) {
+        const uint64_t off[2] = {0, plen}, eoff[2] = {0, extra_commit_len};
+        return secp256k1_rangeproof_verify_batch(e, res, min_value, max_value, (const unsigned char*)commit, proof, off, extra_commit_len ? extra_commit : nullptr,
+                                                 extra_commit_len ? eoff : nullptr, (const unsigned char*)gen, 1);
+    });
 }
 // include/secp256k1_schnorrsig.h:178 -- pubkey points at the 64-byte secp256k1_xonly_pubkey object
 extern "C" int secp256k1_schnorrsig_verify_amd(const void* ctx, const unsigned char* sig64, const unsigned char* msg, size_t msglen, const void* pubkey) {
     (void)ctx;
-    s2k_clear_status();
-    if (!sig64 || (!msg && msglen) || !pubkey) return s2k_fail_arg("secp256k1_schnorrsig_verify_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0; const unsigned char dummy = 0;
-    if (!secp256k1_schnorrsig_verify_batch(e, &res, sig64, msglen ? msg : &dummy, msglen, (const unsigned char*)pubkey, 1, 1)) return 0;
-    return res;
+    return amd_one("secp256k1_schnorrsig_verify_amd", sig64 && (msg || !msglen) && pubkey, [&](s2k_engine* e, int32_t* res) {
+        const unsigned char dummy = 0;
+        return secp256k1_schnorrsig_verify_batch(e, res, sig64, msglen ? msg : &dummy, msglen, (const unsigned char*)pubkey, 1, 1);
+    });
 }
 // include/secp256k1.h:622 -- sig points at the 64-byte secp256k1_ecdsa_signature object, pubkey at the 64-byte secp256k1_pubkey object
 // (the kernels live in engine_ecdsa.hip)
 extern "C" int secp256k1_ecdsa_verify_amd(const void* ctx, const void* sig, const unsigned char* msghash32, const void* pubkey) {
     (void)ctx;
-    s2k_clear_status();
-    if (!sig || !msghash32 || !pubkey) return s2k_fail_arg("secp256k1_ecdsa_verify_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0;
-    if (!secp256k1_ecdsa_verify_batch(e, &res, (const unsigned char*)sig, nullptr, 1, msghash32, (const unsigned char*)pubkey, 1, 1)) return 0;
-    return res;
+    return amd_one("secp256k1_ecdsa_verify_amd", sig && msghash32 && pubkey, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_ecdsa_verify_batch(e, res, (const unsigned char*)sig, nullptr, 1, msghash32, (const unsigned char*)pubkey, 1, 1);
+    });
 }
 // include/secp256k1_ecdsa_adaptor.h (src/modules/ecdsa_adaptor/main_impl.h:236) -- pubkey and enckey point at 64-byte secp256k1_pubkey
 // objects (the kernel lives in engine_adaptor.hip)
 extern "C" int secp256k1_ecdsa_adaptor_verify_amd(const void* ctx, const unsigned char* adaptor_sig162, const void* pubkey, const unsigned char* msg32, const void* enckey) {
     (void)ctx;
-    s2k_clear_status();
-    if (!adaptor_sig162 || !pubkey || !msg32 || !enckey) return s2k_fail_arg("secp256k1_ecdsa_adaptor_verify_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0;
-    if (!secp256k1_ecdsa_adaptor_verify_batch(e, &res, adaptor_sig162, (const unsigned char*)pubkey, msg32, (const unsigned char*)enckey, 1, 1)) return 0;
-    return res;
+    return amd_one("secp256k1_ecdsa_adaptor_verify_amd", adaptor_sig162 && pubkey && msg32 && enckey, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_ecdsa_adaptor_verify_batch(e, res, adaptor_sig162, (const unsigned char*)pubkey, msg32, (const unsigned char*)enckey, 1, 1);
+    });
 }
 // include/secp256k1_ecdsa_s2c.h (src/modules/ecdsa_s2c/main_impl.h:88 and :185) -- sig points at the 64-byte secp256k1_ecdsa_signature
 // object, pubkey and opening at 64-byte secp256k1_pubkey / secp256k1_ecdsa_s2c_opening objects (the kernels live in engine_s2c.hip)
 extern "C" int secp256k1_ecdsa_s2c_verify_commit_amd(const void* ctx, const void* sig, const unsigned char* data32, const void* opening) {
     (void)ctx;
-    s2k_clear_status();
-    if (!sig || !data32 || !opening) return s2k_fail_arg("secp256k1_ecdsa_s2c_verify_commit_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0;
-    if (!secp256k1_ecdsa_s2c_verify_commit_batch(e, &res, (const unsigned char*)sig, nullptr, 1, data32, (const unsigned char*)opening, 1, 1)) return 0;
-    return res;
+    return amd_one("secp256k1_ecdsa_s2c_verify_commit_amd", sig && data32 && opening, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_ecdsa_s2c_verify_commit_batch(e, res, (const unsigned char*)sig, nullptr, 1, data32, (const unsigned char*)opening, 1, 1);
+    });
 }
 extern "C" int secp256k1_anti_exfil_host_verify_amd(const void* ctx, const void* sig, const unsigned char* msg32, const void* pubkey, const unsigned char* host_data32,
                                                     const void* opening) {
     (void)ctx;
-    s2k_clear_status();
-    if (!sig || !msg32 || !pubkey || !host_data32 || !opening) return s2k_fail_arg("secp256k1_anti_exfil_host_verify_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0;
-    if (!secp256k1_anti_exfil_host_verify_batch(e, &res, (const unsigned char*)sig, nullptr, 1, msg32, (const unsigned char*)pubkey, 1, host_data32,
-                                                (const unsigned char*)opening, 1, 1)) return 0;
-    return res;
+    return amd_one("secp256k1_anti_exfil_host_verify_amd", sig && msg32 && pubkey && host_data32 && opening, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_anti_exfil_host_verify_batch(e, res, (const unsigned char*)sig, nullptr, 1, msg32, (const unsigned char*)pubkey, 1, host_data32, (const unsigned char*)opening, 1, 1);
+    });
 }
 // include/secp256k1_ellswift.h (src/modules/ellswift/main_impl.h:470 and :393) -- pubkey points at the 64-byte secp256k1_pubkey object (the
 // kernels live in engine_ellswift.hip)
 extern "C" int secp256k1_ellswift_decode_amd(const void* ctx, void* pubkey, const unsigned char* ell64) {
     (void)ctx;
-    s2k_clear_status();
-    if (!pubkey) return s2k_fail_arg("secp256k1_ellswift_decode_amd", "illegal argument (ARG_CHECK)");
-    memset(pubkey, 0, 64);
-    if (!ell64) return s2k_fail_arg("secp256k1_ellswift_decode_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    if (!secp256k1_ellswift_decode_batch(e, (unsigned char*)pubkey, 1, ell64, 1)) { memset(pubkey, 0, 64); return 0; }
-    return 1;
+    return amd_one("secp256k1_ellswift_decode_amd", pubkey != nullptr, pubkey, 64, ell64 != nullptr, [&](s2k_engine* e, int32_t* res) {
+        *res = 1;                                                                         // (every 64 bytes decode to a key)
+        return secp256k1_ellswift_decode_batch(e, (unsigned char*)pubkey, 1, ell64, 1);
+    });
 }
 extern "C" int secp256k1_ellswift_encode_amd(const void* ctx, unsigned char* ell64, const void* pubkey, const unsigned char* rnd32) {
     (void)ctx;
-    s2k_clear_status();
-    if (!ell64) return s2k_fail_arg("secp256k1_ellswift_encode_amd", "illegal argument (ARG_CHECK)");
-    memset(ell64, 0, 64);
-    if (!pubkey || !rnd32) return s2k_fail_arg("secp256k1_ellswift_encode_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0;
-    if (!secp256k1_ellswift_encode_batch(e, &res, ell64, (const unsigned char*)pubkey, 1, rnd32, 1)) { memset(ell64, 0, 64); return 0; }
-    return res;
+    return amd_one("secp256k1_ellswift_encode_amd", ell64 != nullptr, ell64, 64, pubkey && rnd32, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_ellswift_encode_batch(e, res, ell64, (const unsigned char*)pubkey, 1, rnd32, 1);
+    });
 }
 // include/secp256k1_musig.h (src/modules/musig/session_impl.h:716) -- all five point at the reference's objects (the kernel lives in
 // engine_musig.hip)
 extern "C" int secp256k1_musig_partial_sig_verify_amd(const void* ctx, const void* partial_sig, const void* pubnonce, const void* pubkey, const void* keyagg_cache,
                                                       const void* session) {
     (void)ctx;
-    s2k_clear_status();
-    if (!partial_sig || !pubnonce || !pubkey || !keyagg_cache || !session) return s2k_fail_arg("secp256k1_musig_partial_sig_verify_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0;
-    if (!secp256k1_musig_partial_sig_verify_batch(e, &res, (const unsigned char*)partial_sig, 1, (const unsigned char*)pubnonce, 1, (const unsigned char*)pubkey, 1,
-                                                  (const unsigned char*)keyagg_cache, (const unsigned char*)session, 1, nullptr, 1)) return 0;
-    return res;
+    return amd_one("secp256k1_musig_partial_sig_verify_amd", partial_sig && pubnonce && pubkey && keyagg_cache && session, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_musig_partial_sig_verify_batch(e, res, (const unsigned char*)partial_sig, 1, (const unsigned char*)pubnonce, 1, (const unsigned char*)pubkey, 1,
+                                                        (const unsigned char*)keyagg_cache, (const unsigned char*)session, 1, nullptr, 1);
+    });
 }
 // include/secp256k1_musig.h (src/modules/musig/keyagg_impl.h:156): the objects the pointers name are gathered and take the batch path
-// (the kernels live in engine_musig_agg.hip)
+// (the kernels live in engine_musig_agg.hip).  agg_pk is optional, and zeroed before the keys are looked at.
 extern "C" int secp256k1_musig_pubkey_agg_amd(const void* ctx, void* agg_pk, void* keyagg_cache, const void* const* pubkeys, size_t n_pubkeys) {
     (void)ctx;
-    s2k_clear_status();
-    if (agg_pk) memset(agg_pk, 0, 64);
-    if (!pubkeys || n_pubkeys == 0) return s2k_fail_arg("secp256k1_musig_pubkey_agg_amd", "illegal argument (ARG_CHECK)");
-    for (size_t i = 0; i < n_pubkeys; i++) if (!pubkeys[i]) return s2k_fail_arg("secp256k1_musig_pubkey_agg_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    std::vector<unsigned char> keys(64 * n_pubkeys);
-    for (size_t i = 0; i < n_pubkeys; i++) memcpy(&keys[64 * i], pubkeys[i], 64);
-    const uint64_t off[2] = {0, n_pubkeys};
-    unsigned char cache[197], xo[64];
-    int32_t res = 0;
-    if (!secp256k1_musig_pubkey_agg_batch(e, &res, cache, xo, keys.data(), 1, off, 1)) return 0;
-    if (res && keyagg_cache) memcpy(keyagg_cache, cache, 197);
-    if (res && agg_pk) memcpy(agg_pk, xo, 64);
-    return res;
+    bool keys_ok = pubkeys && n_pubkeys != 0;
+    for (size_t i = 0; keys_ok && i < n_pubkeys; i++) keys_ok = pubkeys[i] != nullptr;
+    return amd_one("secp256k1_musig_pubkey_agg_amd", true, agg_pk, 64, keys_ok, [&](s2k_engine* e, int32_t* res) {
+        std::vector<unsigned char> keys(64 * n_pubkeys);
+        for (size_t i = 0; i < n_pubkeys; i++) memcpy(&keys[64 * i], pubkeys[i], 64);
+        const uint64_t off[2] = {0, n_pubkeys};
+        unsigned char cache[197], xo[64];
+        if (!secp256k1_musig_pubkey_agg_batch(e, res, cache, xo, keys.data(), 1, off, 1)) return 0;
+        if (*res && keyagg_cache) memcpy(keyagg_cache, cache, 197);
+        if (*res && agg_pk) memcpy(agg_pk, xo, 64);
+        return 1;
+    });
 }
 // include/secp256k1_recovery.h:112 -- signature points at the 65-byte secp256k1_ecdsa_recoverable_signature object: the little-endian
 // limbs of r and s, then the recovery id (src/modules/recovery/main_impl.h:13-36); pubkey receives a secp256k1_pubkey object
 extern "C" int secp256k1_ecdsa_recover_amd(const void* ctx, void* pubkey, const void* signature, const unsigned char* msghash32) {
     (void)ctx;
-    s2k_clear_status();
-    if (!pubkey || !signature || !msghash32) return s2k_fail_arg("secp256k1_ecdsa_recover_amd", "illegal argument (ARG_CHECK)");
-    memset(pubkey, 0, 64);
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    const unsigned char* o = (const unsigned char*)signature;
-    unsigned char sig64[64];
-    for (int i = 0; i < 32; i++) { sig64[i] = o[31 - i]; sig64[32 + i] = o[63 - i]; }      // limbs -> compact big-endian
-    int32_t res = 0;
-    if (!secp256k1_ecdsa_recover_batch(e, &res, (unsigned char*)pubkey, sig64, o + 64, msghash32, 1)) { memset(pubkey, 0, 64); return 0; }
-    return res;
+    return amd_one("secp256k1_ecdsa_recover_amd", pubkey && signature && msghash32, pubkey, 64, true, [&](s2k_engine* e, int32_t* res) {
+        const unsigned char* o = (const unsigned char*)signature;
+        unsigned char sig64[64];
+        for (int i = 0; i < 32; i++) { sig64[i] = o[31 - i]; sig64[32 + i] = o[63 - i]; }      // limbs -> compact big-endian
+        return secp256k1_ecdsa_recover_batch(e, res, (unsigned char*)pubkey, sig64, o + 64, msghash32, 1);
+    });
 }
 // include/secp256k1_whitelist.h -- sig points at the secp256k1_whitelist_signature object {size_t n_keys; unsigned char data[32 * 256]},
 // the key arrays at n_keys 64-byte secp256k1_pubkey objects each (the kernels live in engine_whitelist.hip)
 extern "C" int secp256k1_whitelist_verify_amd(const void* ctx, const void* sig, const void* online_pubkeys, const void* offline_pubkeys, size_t n_keys,
                                               const void* sub_pubkey) {
     (void)ctx;
-    s2k_clear_status();
-    if (!sig || !online_pubkeys || !offline_pubkeys || !sub_pubkey) return s2k_fail_arg("secp256k1_whitelist_verify_amd", "illegal argument (ARG_CHECK)");
+    if (!amd_args("secp256k1_whitelist_verify_amd", sig && online_pubkeys && offline_pubkeys && sub_pubkey)) return 0;
     size_t sig_keys; memcpy(&sig_keys, sig, sizeof(size_t));
     if (sig_keys > 255 || sig_keys != n_keys) return 0;                                   // main_impl.h:112-114
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    std::vector<unsigned char> ser(1 + 32 * (sig_keys + 1));                              // secp256k1_whitelist_signature_serialize
-    ser[0] = (unsigned char)sig_keys;
-    memcpy(ser.data() + 1, (const unsigned char*)sig + sizeof(size_t), 32 * (sig_keys + 1));
-    const uint64_t sig_off[2] = {0, ser.size()}, list_off[2] = {0, n_keys};
-    int32_t res = 0;
-    if (!secp256k1_whitelist_verify_batch(e, &res, ser.data(), sig_off, (const unsigned char*)online_pubkeys, (const unsigned char*)offline_pubkeys, list_off, 1,
-                                          nullptr, (const unsigned char*)sub_pubkey, 1)) return 0;
-    return res;
+    return amd_call(nullptr, 0, [&](s2k_engine* e, int32_t* res) {
+        std::vector<unsigned char> ser(1 + 32 * (sig_keys + 1));                          // secp256k1_whitelist_signature_serialize
+        ser[0] = (unsigned char)sig_keys;
+        memcpy(ser.data() + 1, (const unsigned char*)sig + sizeof(size_t), 32 * (sig_keys + 1));
+        const uint64_t sig_off[2] = {0, ser.size()}, list_off[2] = {0, n_keys};
+        return secp256k1_whitelist_verify_batch(e, res, ser.data(), sig_off, (const unsigned char*)online_pubkeys, (const unsigned char*)offline_pubkeys, list_off, 1,
+                                                nullptr, (const unsigned char*)sub_pubkey, 1);
+    });
 }
 // include/secp256k1_extrakeys.h (src/modules/extrakeys/main_impl.h:135) -- internal_pubkey points at the 64-byte secp256k1_xonly_pubkey
 // object (the kernels live in engine_tweak.hip)
 extern "C" int secp256k1_xonly_pubkey_tweak_add_check_amd(const void* ctx, const unsigned char* tweaked_pubkey32, int tweaked_pk_parity, const void* internal_pubkey,
                                                           const unsigned char* tweak32) {
     (void)ctx;
-    s2k_clear_status();
-    if (!internal_pubkey || !tweaked_pubkey32 || !tweak32) return s2k_fail_arg("secp256k1_xonly_pubkey_tweak_add_check_amd", "illegal argument (ARG_CHECK)");
+    if (!amd_args("secp256k1_xonly_pubkey_tweak_add_check_amd", internal_pubkey && tweaked_pubkey32 && tweak32)) return 0;
     if (tweaked_pk_parity != 0 && tweaked_pk_parity != 1) return 0;                       // main_impl.h:153 compares the int: no point can match
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0; const unsigned char par = (unsigned char)tweaked_pk_parity;
-    if (!secp256k1_xonly_pubkey_tweak_add_check_batch(e, &res, tweaked_pubkey32, &par, (const unsigned char*)internal_pubkey, 1, tweak32, 1)) return 0;
-    return res;
+    return amd_call(nullptr, 0, [&](s2k_engine* e, int32_t* res) {
+        const unsigned char par = (unsigned char)tweaked_pk_parity;
+        return secp256k1_xonly_pubkey_tweak_add_check_batch(e, res, tweaked_pubkey32, &par, (const unsigned char*)internal_pubkey, 1, tweak32, 1);
+    });
 }
 // src/modules/extrakeys/main_impl.h:118 -- output_pubkey receives a secp256k1_pubkey object (zeroed first, as :123)
 extern "C" int secp256k1_xonly_pubkey_tweak_add_amd(const void* ctx, void* output_pubkey, const void* internal_pubkey, const unsigned char* tweak32) {
     (void)ctx;
-    s2k_clear_status();
-    if (!output_pubkey) return s2k_fail_arg("secp256k1_xonly_pubkey_tweak_add_amd", "illegal argument (ARG_CHECK)");
-    memset(output_pubkey, 0, 64);
-    if (!internal_pubkey || !tweak32) return s2k_fail_arg("secp256k1_xonly_pubkey_tweak_add_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0;
-    if (!secp256k1_pubkey_tweak_add_batch(e, &res, (unsigned char*)output_pubkey, (const unsigned char*)internal_pubkey, 1, tweak32, 1)) { memset(output_pubkey, 0, 64); return 0; }
-    return res;
+    return amd_one("secp256k1_xonly_pubkey_tweak_add_amd", output_pubkey != nullptr, output_pubkey, 64, internal_pubkey && tweak32, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_pubkey_tweak_add_batch(e, res, (unsigned char*)output_pubkey, (const unsigned char*)internal_pubkey, 1, tweak32, 1);
+    });
 }
 // src/secp256k1.c:773 -- pubkey is read and written; zeroed on failure (:781-782 clears it before the tweak is tried)
 extern "C" int secp256k1_ec_pubkey_tweak_add_amd(const void* ctx, void* pubkey, const unsigned char* tweak32) {
     (void)ctx;
-    s2k_clear_status();
-    if (!pubkey || !tweak32) return s2k_fail_arg("secp256k1_ec_pubkey_tweak_add_amd", "illegal argument (ARG_CHECK)");
-    unsigned char in[64]; memcpy(in, pubkey, 64);
-    memset(pubkey, 0, 64);
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0;
-    if (!secp256k1_pubkey_tweak_add_batch(e, &res, (unsigned char*)pubkey, in, 1, tweak32, 1)) { memset(pubkey, 0, 64); return 0; }
-    return res;
+    unsigned char in[64];
+    if (pubkey) memcpy(in, pubkey, 64);
+    return amd_one("secp256k1_ec_pubkey_tweak_add_amd", pubkey && tweak32, pubkey, 64, true, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_pubkey_tweak_add_batch(e, res, (unsigned char*)pubkey, in, 1, tweak32, 1);
+    });
 }
 // src/modules/generator/main_impl.h:250 -- gen receives a secp256k1_generator object (the kernels live in engine_generator.hip)
 extern "C" int secp256k1_generator_generate_amd(const void* ctx, void* gen, const unsigned char* key32) {
     (void)ctx;
-    s2k_clear_status();
-    if (!gen) return s2k_fail_arg("secp256k1_generator_generate_amd", "illegal argument (ARG_CHECK)");
-    memset(gen, 0, 64);
-    if (!key32) return s2k_fail_arg("secp256k1_generator_generate_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0;
-    if (!secp256k1_generator_generate_batch(e, &res, (unsigned char*)gen, key32, nullptr, 1)) { memset(gen, 0, 64); return 0; }
-    return res;
+    return amd_one("secp256k1_generator_generate_amd", gen != nullptr, gen, 64, key32 != nullptr, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_generator_generate_batch(e, res, (unsigned char*)gen, key32, nullptr, 1);
+    });
 }
 // src/modules/generator/main_impl.h:59
 extern "C" int secp256k1_generator_parse_amd(const void* ctx, void* gen, const unsigned char* input33) {
     (void)ctx;
-    s2k_clear_status();
-    if (!gen) return s2k_fail_arg("secp256k1_generator_parse_amd", "illegal argument (ARG_CHECK)");
-    memset(gen, 0, 64);
-    if (!input33) return s2k_fail_arg("secp256k1_generator_parse_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0;
-    if (!secp256k1_generator_parse_batch(e, &res, (unsigned char*)gen, input33, 1)) { memset(gen, 0, 64); return 0; }
-    return res;
+    return amd_one("secp256k1_generator_parse_amd", gen != nullptr, gen, 64, input33 != nullptr, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_generator_parse_batch(e, res, (unsigned char*)gen, input33, 1);
+    });
 }
 // src/modules/generator/main_impl.h:309 -- commit receives the first 33 bytes of a secp256k1_pedersen_commitment object, the rest zeroed.
 // The blind is treated as public data: nothing here is constant time.
 extern "C" int secp256k1_pedersen_commit_amd(const void* ctx, void* commit, const unsigned char* blind, uint64_t value, const void* gen) {
     (void)ctx;
-    s2k_clear_status();
-    if (!commit) return s2k_fail_arg("secp256k1_pedersen_commit_amd", "illegal argument (ARG_CHECK)");
-    memset(commit, 0, 64);
-    if (!blind || !gen) return s2k_fail_arg("secp256k1_pedersen_commit_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    int32_t res = 0;
-    if (!secp256k1_pedersen_commit_batch(e, &res, (unsigned char*)commit, blind, &value, (const unsigned char*)gen, 1)) { memset(commit, 0, 64); return 0; }
-    return res;
+    return amd_one("secp256k1_pedersen_commit_amd", commit != nullptr, commit, 64, blind && gen, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_pedersen_commit_batch(e, res, (unsigned char*)commit, blind, &value, (const unsigned char*)gen, 1);
+    });
 }
 // include/secp256k1_generator.h:190 -- arrays of pointers to 64-byte secp256k1_pedersen_commitment objects
 extern "C" int secp256k1_pedersen_verify_tally_amd(const void* ctx, const void* const* commits, size_t pcnt, const void* const* ncommits, size_t ncnt) {
     (void)ctx;
-    s2k_clear_status();
-    if ((!commits && pcnt) || (!ncommits && ncnt)) return s2k_fail_arg("secp256k1_pedersen_verify_tally_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    std::vector<unsigned char> c33(33 * (pcnt + ncnt) + 1);
-    for (size_t i = 0; i < pcnt; i++) memcpy(&c33[33 * i], commits[i], 33);
-    for (size_t i = 0; i < ncnt; i++) memcpy(&c33[33 * (pcnt + i)], ncommits[i], 33);
-    const uint64_t off[2] = {0, pcnt + ncnt}, npos[1] = {pcnt};
-    int32_t res = 0;
-    if (!secp256k1_pedersen_verify_tally_batch(e, &res, c33.data(), off, npos, 1)) return 0;
-    return res;
+    return amd_one("secp256k1_pedersen_verify_tally_amd", (commits || !pcnt) && (ncommits || !ncnt), [&](s2k_engine* e, int32_t* res) {
+        std::vector<unsigned char> c33(33 * (pcnt + ncnt) + 1);
+        for (size_t i = 0; i < pcnt; i++) memcpy(&c33[33 * i], commits[i], 33);
+        for (size_t i = 0; i < ncnt; i++) memcpy(&c33[33 * (pcnt + i)], ncommits[i], 33);
+        const uint64_t off[2] = {0, pcnt + ncnt}, npos[1] = {pcnt};
+        return secp256k1_pedersen_verify_tally_batch(e, res, c33.data(), off, npos, 1);
+    });
 }
 // include/secp256k1_surjectionproof.h:256 -- proof points at a secp256k1_surjectionproof object (:50-62 of that header:
 // size_t n_inputs; unsigned char used_inputs[256/8]; unsigned char data[32*(1+256)]), tags at arrays of 64-byte generators.
@@ -999,24 +947,20 @@ extern "C" int secp256k1_pedersen_verify_tally_amd(const void* ctx, const void* 
 extern "C" int secp256k1_surjectionproof_verify_amd(const void* ctx, const void* proof, const void* ephemeral_input_tags, size_t n_ephemeral_input_tags,
                                                     const void* ephemeral_output_tag) {
     (void)ctx;
-    s2k_clear_status();
-    if (!proof || !ephemeral_input_tags || !ephemeral_output_tag) return s2k_fail_arg("secp256k1_surjectionproof_verify_amd", "illegal argument (ARG_CHECK)");
-    s2k_engine* e = default_engine();
-    if (!e) return 0;
-    struct sj_obj { size_t n_inputs; unsigned char used[32]; unsigned char data[32 * 257]; };
-    const sj_obj* o = (const sj_obj*)proof;
-    if (o->n_inputs > 256) return 0;
-    const size_t bm = (o->n_inputs + 7) / 8;
-    size_t used = 0;
-    for (size_t i = 0; i < bm; i++) used += (size_t)__builtin_popcount(o->used[i]);
-    std::vector<unsigned char> ser(2 + bm + 32 * (1 + used));
-    ser[0] = (unsigned char)(o->n_inputs & 0xFF); ser[1] = (unsigned char)(o->n_inputs >> 8);
-    memcpy(&ser[2], o->used, bm);
-    memcpy(&ser[2 + bm], o->data, 32 * (1 + used));
-    const uint64_t poff[2] = {0, ser.size()}, toff[2] = {0, n_ephemeral_input_tags};
-    int32_t res = 0;
-    if (!secp256k1_surjectionproof_verify_batch(e, &res, ser.data(), poff, (const unsigned char*)ephemeral_input_tags, toff, (const unsigned char*)ephemeral_output_tag, 1)) return 0;
-    return res;
+    return amd_one("secp256k1_surjectionproof_verify_amd", proof && ephemeral_input_tags && ephemeral_output_tag, [&](s2k_engine* e, int32_t* res) {
+        struct sj_obj { size_t n_inputs; unsigned char used[32]; unsigned char data[32 * 257]; };
+        const sj_obj* o = (const sj_obj*)proof;
+        if (o->n_inputs > 256) return 1;                                                  // (res stays 0)
+        const size_t bm = (o->n_inputs + 7) / 8;
+        size_t used = 0;
+        for (size_t i = 0; i < bm; i++) used += (size_t)__builtin_popcount(o->used[i]);
+        std::vector<unsigned char> ser(2 + bm + 32 * (1 + used));
+        ser[0] = (unsigned char)(o->n_inputs & 0xFF); ser[1] = (unsigned char)(o->n_inputs >> 8);
+        memcpy(&ser[2], o->used, bm);
+        memcpy(&ser[2 + bm], o->data, 32 * (1 + used));
+        const uint64_t poff[2] = {0, ser.size()}, toff[2] = {0, n_ephemeral_input_tags};
+        return secp256k1_surjectionproof_verify_batch(e, res, ser.data(), poff, (const unsigned char*)ephemeral_input_tags, toff, (const unsigned char*)ephemeral_output_tag, 1);
+    });
 }
 
 // engine options (include/secp256k1_zkp_amd.h)
@@ -1388,18 +1332,11 @@ static int group_msm(s2k_group* g, const char* who, unsigned char* r_xy, int32_t
             hipStream_t st = e->stream;
             const unsigned char *d_sc = sci, *d_pt = pti, *d_inf = infi, *d_g = gs;
             if (!resident) {
-                // slice to HBM: behind the MSM's own workspace need (s2k_ecmult_multi_partial_dev carves from the start)
-                const size_t nt = m + (gs ? 1 : 0);
-                const size_t base = ws_need({28 * 4}) + msm_ws_bytes(e, nt + 1, engine_msm_plan(e, nt ? nt : 1));
-                if (!engine_workspace(e, base + ws_need({32 * m + 64, 64 * m + 64, m + 64, 64}))) return 0;
-                ws_carver c{e->ws, base};
-                unsigned char* a = c.take<unsigned char>(32 * m + 64); unsigned char* b = c.take<unsigned char>(64 * m + 64); unsigned char* ci = c.take<unsigned char>(m + 64);
-                unsigned char* dg = c.take<unsigned char>(64);
-                stream_guard sg(e, st);
-                if (m) { HIPCHK(hipMemcpyAsync(a, sci, 32 * m, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(b, pti, 64 * m, hipMemcpyHostToDevice, st)); }
-                if (m && infi) HIPCHK(hipMemcpyAsync(ci, infi, m, hipMemcpyHostToDevice, st));
-                if (gs) HIPCHK(hipMemcpyAsync(dg, gs, 32, hipMemcpyHostToDevice, st));
-                d_sc = a; d_pt = b; d_inf = infi ? ci : nullptr; d_g = gs ? dg : nullptr;
+                // slice to HBM: behind the workspace of s2k_ecmult_multi_partial_dev, which carves from the start (no stage_close: the
+                // result leaves by the peer copy)
+                stage_buf b[] = {{sci, nullptr, 32 * m, 64}, {pti, nullptr, 64 * m, 64}, {infi, nullptr, m, 64}, {gs, nullptr, 32}};
+                if (!stage_open(e, b, msm_run_ws_bytes(e, m, gs != nullptr))) return 0;
+                d_sc = b[0].at(); d_pt = b[1].at(); d_inf = b[2].opt(); d_g = b[3].opt();
             }
             if (!s2k_ecmult_multi_partial_dev(e, nullptr, part, d_g, d_sc, d_pt, d_inf, m)) return 0;
             HIPCHK(hipMemcpyPeerAsync(dst, dev0, part, e->device, 28 * sizeof(u32), st));

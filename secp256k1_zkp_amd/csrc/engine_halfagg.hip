@@ -184,10 +184,10 @@ extern "C" int secp256k1_schnorrsig_aggverify_amd(s2k_engine* e, int32_t* result
     HIPCHK(hipSetDevice(e->device));
     const size_t pkb = pk_format ? 64 : 32;
     hipStream_t st = e->stream;
-    stream_guard sg(e, st);
     // the device part at 0, the buffers behind it
     stage_buf b[] = {{pubkeys, nullptr, pkb * n, 64}, {msgs32, nullptr, 32 * n, 64}, {aggsig, nullptr, 32 * (n + 1)}, {nullptr, result, 4, 12}};
     if (!stage_open(e, b, ha_ws_bytes(e, n))) return 0;
+    stream_guard sg(e, st);
     ws_carver c{e->ws, 0};
     const int host_chain = e->halfagg_host_chain;      // S2K_OPT_HALFAGG_HOST_CHAIN 0: the device chain (same verdicts; tests)
     const ha_host_src hsrc{aggsig, pubkeys, pk_format, msgs32};

@@ -143,11 +143,11 @@ extern "C" int secp256k1_schnorrsig_aggverify_batch(s2k_engine* e, int32_t* resu
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = e->stream;
-    stream_guard sg(e, st);
     const size_t K = n_aggs, N = (size_t)item_off[K], A = (size_t)aggsig_off[K], pkb = pk_format ? 64 : 32;
     const hab_verify_plan p = hab_plan_verify(item_off, aggsig_off, K, MM_MAX_TERMS);
     stage_buf b[] = {{pubkeys, nullptr, pkb * N, 64}, {msgs32, nullptr, 32 * N, 64}, {aggsigs, nullptr, A, 64}, {nullptr, results, 4 * K, 64}};
     if (!stage_open(e, b, 0, hab_verify_ws(e, hab_sizes(item_off, K, p), p, item_off))) return 0;
+    stream_guard sg(e, st);
     return stage_close(e, b, hab_verify_run(e, st, stage_bytes(b), b[3].at<int32_t>(), b[0].at(), pk_format, b[1].at(), b[2].at(), item_off, aggsig_off, K, p));
 }
 
@@ -235,11 +235,11 @@ static int hab_agg_host(const char* who, int inc, s2k_engine* e, int32_t* result
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = e->stream;
-    stream_guard sg(e, st);
     const size_t N = p.N, pkb = pk_format ? 64 : 32;
     stage_buf b[] = {{nullptr, results, 4 * K, 64}, {nullptr, out, 32 * (N + K), 64}, {aggsigs_in, nullptr, p.in_bytes, 64}, {pks, nullptr, pkb * N, 64},
                      {msgs32, nullptr, 32 * N, 64}, {new_sigs64, nullptr, 64 * p.n_new, 64}};
     if (!stage_open(e, b, 0, hab_agg_ws(p))) return 0;
+    stream_guard sg(e, st);
     return stage_close(e, b, hab_agg_run(e, st, stage_bytes(b), b[0].at<int32_t>(), b[1].at(), b[2].opt(), inc, b[3].at(), pk_format, b[4].at(), b[5].opt(), p));
 }
 extern "C" int secp256k1_schnorrsig_inc_aggregate_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* aggsigs_out, const unsigned char* aggsigs_in,

@@ -23,9 +23,10 @@
 //   engine_schnorr_all.hip one-verdict batch verification of BIP-340 signatures as a single multi-scalar multiplication (schnorr_all.h)
 //   engine_bppp_all.hip    one-verdict batch verification of BP++ norm arguments over one generator set as a single multi-scalar multiplication (bppp_all.h)
 // What a family does around its kernels is engine_lanes.h (host code only, included by the units that use it): lanes_run behind the
-// `_dev` forms of the one-item-per-lane families, stage_open / stage_close behind the host-buffer forms of every family but MSM and
-// rangeproof (each staged buffer named once, beside the device part's own workspace where there is one), der_window for DER-packed
-// signatures; the `_group` forms that split a batch by items go through group_by_items (engine_core.hip).  What the verifiers that answer
+// `_dev` forms of the one-item-per-lane families, stage_open / stage_close behind the host-buffer forms of every family (each staged
+// buffer named once, beside the device part's own workspace where there is one; the stager orders its uploads behind the engine's last
+// work on another stream) -- all but rangeproof verification, whose pinned, pipelined staging is rp_host_submit -- der_window for
+// DER-packed signatures; the `_group` forms that split a batch by items go through group_by_items (engine_core.hip).  What the verifiers that answer
 // a batch with one verdict share (engine_schnorr_all, engine_bppp_all, the final kernel also engine_halfagg) is engine_verdict.h: the hash
 // tree's node kernel and level loop, the MSM behind stand-in events, the final kernel, the split times and the host sequence.  The families
 // with a workspace of their own (MSM, rangeproof, BP++, half-aggregates, whitelist, the one-verdict verifiers, MuSig aggregation) carve
@@ -269,6 +270,8 @@ struct msm_out { unsigned char* r_xy; int32_t* r_inf; u32* out28; };
 size_t msm_max_terms(const s2k_engine* e);
 msm_plan engine_msm_plan(const s2k_engine* e, size_t nt);
 size_t msm_ws_bytes(const s2k_engine* e, size_t nt, const msm_plan& pl);
+// workspace of one sum of n terms (+ the generator's) through s2k_ecmult_multi_dev / _partial_dev, whatever its size (msm_run)
+size_t msm_run_ws_bytes(const s2k_engine* e, size_t n, int has_g);
 // core of every MSM entry point: leaves the Jacobian result (28 words) at *result28 (device), stream-ordered, nothing read back
 int msm_launch(s2k_engine* e, hipStream_t st, ws_carver& c, u32** result28, const unsigned char* g_sc, const unsigned char* sc,
                const unsigned char* pt, const unsigned char* pt_inf, size_t n, u32 part = 0, u32 parts = 1, const msm_ctx* ctx = nullptr, const msm_out* out = nullptr);

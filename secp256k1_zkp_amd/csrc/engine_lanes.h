@@ -1,7 +1,11 @@
 // engine_lanes.h -- what a family does around its kernels, written once (host code only):
 //   lanes_run               the `_dev` form of a one-item-per-lane family: device, lock, stream, tables, zeroed outputs, events, the sub-range loop
 //   stage_open / _close     the host-buffer form of every family: each buffer named once, carved from the workspace (beside the device part's
-//                           own workspace, where it has one), uploaded, downloaded
+//                           own workspace, where it has one), uploaded, downloaded.  The stager owns the ordering of its uploads: stage_open
+//                           first makes e->stream wait for the engine's last work when that was queued on another stream (stream_guard),
+//                           so a host form opens no guard of its own in front of it.
+//                           (Not staged here: the rangeproof verify host path, rp_host_submit / rp_host_wait -- pinned staging sets, a copy
+//                           stream, two batches in flight and a lifetime that outlasts the call.)
 //   der_window              the bytes and rebased offsets of a DER-packed signature array
 // An entry point keeps its own prologue (who, null engine, n == 0, ARG_CHECK, formats) and hands the rest to these.
 #pragma once
@@ -67,12 +71,15 @@ template <size_t N>
 static size_t stage_bytes(const stage_buf (&b)[N]) { return (stage_end(b) + 255) & ~size_t(255); }
 // sizes the workspace, carves the buffers in order from offset lo and queues the uploads on e->stream.  A form whose device part has a
 // workspace of its own says where it lies: in front of the buffers ([0, lo): the carves that start at 0 again, such as a locating call's)
-// or behind them (extra bytes from stage_bytes(b) on; lo = 0).
+// or behind them (extra bytes from stage_bytes(b) on; lo = 0).  The uploads overwrite a workspace that the call before this one may still
+// be reading on a caller's stream: they are queued under a stream_guard, which leaves last_stream == e->stream, so the guard that the
+// device part opens next (the `_dev` form's own, or the host form's behind stage_open) finds nothing to wait for.
 template <size_t N>
 static int stage_open(s2k_engine* e, stage_buf (&b)[N], size_t lo = 0, size_t extra = 0) {
     if (!engine_workspace(e, lo + stage_end(b) + 256 + extra)) return 0;      // (sized once: growing the workspace moves it)
     ws_carver w{e->ws, lo};
     for (stage_buf& s : b) s.dev = w.take<unsigned char>(s.bytes + s.pad);
+    stream_guard sg(e, e->stream);
     for (const stage_buf& s : b) if (s.in && s.bytes) HIPCHK(hipMemcpyAsync(s.dev, s.in, s.bytes, hipMemcpyHostToDevice, e->stream));
     return 1;
 }

@@ -1,4 +1,4 @@
-#include "engine_internal.h"
+#include "engine_lanes.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // multi-scalar multiplication (msm.h)
@@ -1134,7 +1134,7 @@ static int msm_pipelined(s2k_engine* e, hipStream_t st, int finish, uint32_t* ou
 // than msm_max_terms() terms goes as consecutive launches over slices of the term arrays whose Jacobian partial sums are added at the end --
 // the reference's own treatment of a sum that exceeds its scratch space (ecmult_impl.h:804-820 computes the batch size, :856-865 loops over
 // the batches and adds).  `front`: bytes of the workspace the caller has already carved (staged inputs).
-static size_t msm_run_ws_bytes(const s2k_engine* e, size_t n, int has_g) {
+size_t msm_run_ws_bytes(const s2k_engine* e, size_t n, int has_g) {
     const size_t nt = n + (has_g ? 1 : 0), cap = msm_max_terms(e);
     if (nt <= cap) return msm_ws_bytes(e, nt + 1, engine_msm_plan(e, nt ? nt : 1));
     const size_t per = has_g ? cap - 1 : cap, pieces = (n + per - 1) / per;
@@ -1237,25 +1237,12 @@ extern "C" int s2k_ecmult_multi(s2k_engine* e, unsigned char* r_xy, int32_t* r_i
     if (!r_xy || !r_inf || (n && (!sc || !pt_xy))) return s2k_fail_arg("s2k_ecmult_multi", "illegal argument (ARG_CHECK)");
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    // the staged inputs come first in the workspace, the MSM passes carve what follows (sized here, once: growing the workspace moves it)
-    const size_t front = ws_need({32 * n + 64, 64 * n + 64, n + 64, 64, 64, 16});
-    if (!engine_workspace(e, front + msm_run_ws_bytes(e, n, g_sc != nullptr))) return 0;
-    ws_carver c{e->ws, 0};
-    unsigned char* d_sc = c.take<unsigned char>(32 * n + 64); unsigned char* d_pt = c.take<unsigned char>(64 * n + 64); unsigned char* d_inf = c.take<unsigned char>(n + 64);
-    unsigned char* d_g = c.take<unsigned char>(64); unsigned char* d_r = c.take<unsigned char>(64); int32_t* d_ri = c.take<int32_t>(4);
+    // the staged inputs come first in the workspace, the MSM passes carve what follows
+    stage_buf b[] = {{sc, nullptr, 32 * n, 64}, {pt_xy, nullptr, 64 * n, 64}, {pt_inf, nullptr, n, 64}, {g_sc, nullptr, 32}, {nullptr, r_xy, 64}, {nullptr, r_inf, 4}};
+    if (!stage_open(e, b, 0, msm_run_ws_bytes(e, n, g_sc != nullptr))) return 0;
     hipStream_t st = e->stream;
     stream_guard sg(e, st);
-    if (n) {
-        HIPCHK(hipMemcpyAsync(d_sc, sc, 32 * n, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_pt, pt_xy, 64 * n, hipMemcpyHostToDevice, st));
-        if (pt_inf) HIPCHK(hipMemcpyAsync(d_inf, pt_inf, n, hipMemcpyHostToDevice, st));
-    }
-    if (g_sc) HIPCHK(hipMemcpyAsync(d_g, g_sc, 32, hipMemcpyHostToDevice, st));
-    if (!msm_run(e, st, front, msm_out{d_r, d_ri, nullptr}, g_sc ? d_g : nullptr, d_sc, d_pt, pt_inf ? d_inf : nullptr, n)) return 0;
-    HIPCHK(hipMemcpyAsync(r_xy, d_r, 64, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(r_inf, d_ri, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
+    return stage_close(e, b, msm_run(e, st, stage_bytes(b), msm_out{b[4].at(), b[5].at<int32_t>(), nullptr}, b[3].opt(), b[0].at(), b[1].at(), b[2].opt(), n));
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1279,21 +1266,9 @@ __global__ void k_pt_final(int32_t* results, const u32* sums28, const u32* off_l
     if (off_last[t + 1] > off_last[t]) inf = (int)sums28[(size_t)off_last[t] * 28 + 27];
     results[t] = inf && !bad[t];
 }
-// dev = 1: `results` and `commits33` are device pointers (the two small offset arrays always come from the host: the run
-// lengths of every partial-sum round are derived from them before anything is launched) and nothing is read back
-static int tally_impl(s2k_engine* e, void* stream, int32_t* results, const unsigned char* commits33, const uint64_t* tally_off,
-                      const uint64_t* n_pos, size_t n_tallies, int dev) {
-    if (!e) return s2k_fail("secp256k1_pedersen_verify_tally_batch", "null engine");
-    if (n_tallies == 0) return 1;
-    if (!results || !tally_off || !n_pos) return s2k_fail_arg("secp256k1_pedersen_verify_tally_batch", "illegal argument (ARG_CHECK)");
-    if (!dev) memset(results, 0, sizeof(int32_t) * n_tallies);
-    const size_t total = (size_t)tally_off[n_tallies];
-    if (total >= ((size_t)1 << 32)) return s2k_fail("secp256k1_pedersen_verify_tally_batch", "more than 2^32 commitments in one call");
-    for (size_t t = 0; t < n_tallies; t++)
-        if (tally_off[t + 1] < tally_off[t] || n_pos[t] > tally_off[t + 1] - tally_off[t]) return s2k_fail("secp256k1_pedersen_verify_tally_batch", "malformed tally offsets");
-    if (total && !commits33) return s2k_fail_arg("secp256k1_pedersen_verify_tally_batch", "illegal argument (ARG_CHECK)");
-    // the offset arrays of every partial-sum round are known from the sizes alone: built here, uploaded once
-    const u32 T = 8;
+// the offset arrays of every partial-sum round (runs of PT_RUN) are known from the sizes alone: [0] the commitments of every tally
+#define PT_RUN 8u
+static std::vector<std::vector<u32>> tally_rounds(const uint64_t* tally_off, size_t n_tallies) {
     std::vector<std::vector<u32>> offs;
     { std::vector<u32> o(n_tallies + 1); for (size_t t = 0; t <= n_tallies; t++) o[t] = (u32)tally_off[t]; offs.push_back(o); }
     for (;;) {
@@ -1301,51 +1276,76 @@ static int tally_impl(s2k_engine* e, void* stream, int32_t* results, const unsig
         u32 mx = 0; for (size_t t = 0; t < n_tallies; t++) mx = std::max(mx, in[t + 1] - in[t]);
         if (mx <= 1) break;
         std::vector<u32> o(n_tallies + 1); o[0] = 0;
-        for (size_t t = 0; t < n_tallies; t++) o[t + 1] = o[t] + (in[t + 1] - in[t] + T - 1) / T;
+        for (size_t t = 0; t < n_tallies; t++) o[t + 1] = o[t] + (in[t + 1] - in[t] + PT_RUN - 1) / PT_RUN;
         offs.push_back(o);
     }
+    return offs;
+}
+// the `_dev` form's workspace, carved from offset 0
+static size_t tally_ws_bytes(const std::vector<std::vector<u32>>& offs, size_t n_tallies) {
+    const size_t total = offs[0][n_tallies], half = offs.size() > 1 ? (size_t)offs[1][n_tallies] : 1;
+    return ws_need({8 * (n_tallies + 1), 8 * n_tallies + 8, 4 * n_tallies + 4, offs.size() * (n_tallies + 1) * 4 + 256 * offs.size(), (total + 1) * 28 * 4, (half + 1) * 28 * 4});
+}
+// what both forms check behind their NULL checks (the messages name the host form)
+static int tally_shape_ok(const unsigned char* commits33, const uint64_t* tally_off, const uint64_t* n_pos, size_t n_tallies) {
+    const size_t total = (size_t)tally_off[n_tallies];
+    if (total >= ((size_t)1 << 32)) return s2k_fail("secp256k1_pedersen_verify_tally_batch", "more than 2^32 commitments in one call");
+    for (size_t t = 0; t < n_tallies; t++)
+        if (tally_off[t + 1] < tally_off[t] || n_pos[t] > tally_off[t + 1] - tally_off[t]) return s2k_fail("secp256k1_pedersen_verify_tally_batch", "malformed tally offsets");
+    if (total && !commits33) return s2k_fail_arg("secp256k1_pedersen_verify_tally_batch", "illegal argument (ARG_CHECK)");
+    return 1;
+}
+// `results` and `commits33` are device pointers; the two small offset arrays always come from the host (the run lengths of every
+// partial-sum round are derived from them before anything is launched).  Nothing is read back.
+extern "C" int secp256k1_pedersen_verify_tally_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* commits33, const uint64_t* tally_off,
+                                                         const uint64_t* n_pos, size_t n_tallies) {
+    if (!e) return s2k_fail("secp256k1_pedersen_verify_tally_batch", "null engine");
+    if (n_tallies == 0) return 1;
+    if (!results || !tally_off || !n_pos) return s2k_fail_arg("secp256k1_pedersen_verify_tally_batch", "illegal argument (ARG_CHECK)");
+    if (!tally_shape_ok(commits33, tally_off, n_pos, n_tallies)) return 0;
+    const size_t total = (size_t)tally_off[n_tallies];
+    const std::vector<std::vector<u32>> offs = tally_rounds(tally_off, n_tallies);      // built here, uploaded once
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    const size_t half = (size_t)offs.size() > 1 ? (size_t)offs[1][n_tallies] : 1;
-    if (!engine_workspace(e, ws_need({33 * total + 64, 8 * (n_tallies + 1), 8 * n_tallies + 8, 4 * n_tallies, 4 * n_tallies + 4, offs.size() * (n_tallies + 1) * 4 + 256 * offs.size(),
-                                      (total + 1) * 28 * 4, (half + 1) * 28 * 4}))) return 0;
+    const size_t half = offs.size() > 1 ? (size_t)offs[1][n_tallies] : 1;
+    if (!engine_workspace(e, tally_ws_bytes(offs, n_tallies))) return 0;
     ws_carver c{e->ws, 0};
-    unsigned char* d_c = c.take<unsigned char>(33 * total + 64); unsigned long long* d_off = c.take<unsigned long long>(n_tallies + 1);
-    unsigned long long* d_np = c.take<unsigned long long>(n_tallies + 1); int32_t* d_res = c.take<int32_t>(n_tallies); u32* d_bad = c.take<u32>(n_tallies + 1);
+    unsigned long long* d_off = c.take<unsigned long long>(n_tallies + 1); unsigned long long* d_np = c.take<unsigned long long>(n_tallies + 1); u32* d_bad = c.take<u32>(n_tallies + 1);
     std::vector<u32*> d_offs; for (size_t r = 0; r < offs.size(); r++) d_offs.push_back(c.take<u32>(n_tallies + 1));
     u32* bufA = c.take<u32>((total + 1) * 28); u32* bufB = c.take<u32>((half + 1) * 28);
-    hipStream_t st = (dev && stream) ? (hipStream_t)stream : e->stream;
+    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
     stream_guard sg(e, st);
-    if (dev) { d_c = (unsigned char*)commits33; d_res = results; }
-    else if (total) HIPCHK(hipMemcpyAsync(d_c, commits33, 33 * total, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_off, tally_off, 8 * (n_tallies + 1), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_np, n_pos, 8 * n_tallies, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_bad, 0, 4 * (n_tallies + 1), st));
     for (size_t r = 0; r < offs.size(); r++) HIPCHK(hipMemcpyAsync(d_offs[r], offs[r].data(), 4 * (n_tallies + 1), hipMemcpyHostToDevice, st));
-    if (dev) HIPCHK(hipEventRecord(e->ev_fork, st));           // the host-side offset arrays must have been consumed before this call returns
+    HIPCHK(hipEventRecord(e->ev_fork, st));                    // the host-side offset arrays must have been consumed before this call returns
     HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
-    if (total) hipLaunchKernelGGL(k_pt_load, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, bufA, d_bad, d_c, d_off, d_np, n_tallies, total);
+    if (total) hipLaunchKernelGGL(k_pt_load, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, bufA, d_bad, commits33, d_off, d_np, n_tallies, total);
     HIPCHK(hipEventRecord(e->ev[3], st));
     u32 *pin = bufA, *pout = bufB;
     for (size_t r = 1; r < offs.size(); r++) {
         const size_t lanes = offs[r][n_tallies];
-        hipLaunchKernelGGL(k_msm_roundN, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, pout, pin, d_offs[r - 1], d_offs[r], (u32)n_tallies, T);
+        hipLaunchKernelGGL(k_msm_roundN, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, pout, pin, d_offs[r - 1], d_offs[r], (u32)n_tallies, PT_RUN);
         u32* tmp = pin; pin = pout; pout = tmp;
     }
-    hipLaunchKernelGGL(k_pt_final, dim3((unsigned)((n_tallies + 255) / 256)), dim3(256), 0, st, d_res, pin, d_offs.back(), d_bad, n_tallies);
+    hipLaunchKernelGGL(k_pt_final, dim3((unsigned)((n_tallies + 255) / 256)), dim3(256), 0, st, results, pin, d_offs.back(), d_bad, n_tallies);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e->ev[1], st));
-    if (dev) { HIPCHK(hipEventSynchronize(e->ev_fork)); return 1; }
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n_tallies, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipEventSynchronize(e->ev_fork));
     return 1;
 }
+// host buffers: the commitments and the results lie behind the `_dev` form's scratch
 extern "C" int secp256k1_pedersen_verify_tally_batch(s2k_engine* e, int32_t* results, const unsigned char* commits33, const uint64_t* tally_off,
                                                      const uint64_t* n_pos, size_t n_tallies) {
-    return tally_impl(e, nullptr, results, commits33, tally_off, n_pos, n_tallies, 0);
+    if (!e) return s2k_fail("secp256k1_pedersen_verify_tally_batch", "null engine");
+    if (n_tallies == 0) return 1;
+    if (!results || !tally_off || !n_pos) return s2k_fail_arg("secp256k1_pedersen_verify_tally_batch", "illegal argument (ARG_CHECK)");
+    memset(results, 0, sizeof(int32_t) * n_tallies);
+    if (!tally_shape_ok(commits33, tally_off, n_pos, n_tallies)) return 0;
+    std::lock_guard<std::recursive_mutex> lock(e->mu);
+    HIPCHK(hipSetDevice(e->device));
+    stage_buf b[] = {{commits33, nullptr, 33 * (size_t)tally_off[n_tallies], 64}, {nullptr, results, 4 * n_tallies}};
+    if (!stage_open(e, b, tally_ws_bytes(tally_rounds(tally_off, n_tallies), n_tallies))) return 0;
+    return stage_close(e, b, secp256k1_pedersen_verify_tally_batch_dev(e, nullptr, b[1].at<int32_t>(), b[0].at(), tally_off, n_pos, n_tallies));
 }
-extern "C" int secp256k1_pedersen_verify_tally_batch_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* commits33, const uint64_t* tally_off_host,
-                                                         const uint64_t* n_pos_host, size_t n_tallies) {
-    return tally_impl(e, stream, results, commits33, tally_off_host, n_pos_host, n_tallies, 1);
-}
-

@@ -291,9 +291,9 @@ extern "C" int s2k_ecmult_multi_many(s2k_engine* e, unsigned char* r_xy, int32_t
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = e->stream;
-    stream_guard sg(e, st);
     stage_buf b[] = {{sc, nullptr, 32 * n, 64}, {pt_xy, nullptr, 64 * n, 64}, {pt_inf, nullptr, n, 64}, {g_sc, nullptr, 32 * K, 64}, {nullptr, r_xy, 64 * K, 64}, {nullptr, r_inf, 4 * K, 64}};
     if (!stage_open(e, b, 0, mm_ws_bytes(e, offsets, K, g_sc ? 1u : 0u))) return 0;
+    stream_guard sg(e, st);
     HIPCHK(hipEventRecord(e->ev[0], st));
     const int ok = mm_impl(e, st, stage_bytes(b), b[4].at(), b[5].at<int32_t>(), b[3].opt(), b[0].at(), b[1].at(), b[2].opt(), offsets, K);
     if (ok) HIPCHK(hipEventRecord(e->ev[1], st));

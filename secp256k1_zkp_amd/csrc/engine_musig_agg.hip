@@ -203,11 +203,11 @@ extern "C" int secp256k1_musig_pubkey_agg_batch(s2k_engine* e, int32_t* results,
     if (!keyagg_args(who, pubkeys, pk_format, set_off, n_sets)) return 0;
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    stream_guard sg(e, e->stream);
     const size_t n_keys = (size_t)set_off[n_sets], pkb = ecdsa_pk_bytes(pk_format), cb = (size_t)MUSIG_CACHE_BYTES * n_sets;
     const agg_sum_plan p = musig_agg_plan_sum(set_off, n_sets, agg_fanin(e));
     stage_buf b[] = {{nullptr, results, 4 * n_sets}, {nullptr, caches_out197, cb}, {nullptr, agg_pks_out64, 64 * n_sets}, {pubkeys, nullptr, pkb * n_keys}};
     if (!stage_open(e, b, 0, keyagg_ws(p, n_keys, n_sets))) return 0;
+    stream_guard sg(e, e->stream);
     ws_carver w{e->ws, stage_bytes(b)};
     return stage_close(e, b, keyagg_run(e, e->stream, w, p, b[0].at<int32_t>(), b[1].at(), agg_pks_out64 ? b[2].at() : nullptr, b[3].at(), pk_format, n_sets));
 }
@@ -315,11 +315,11 @@ extern "C" int secp256k1_musig_nonce_agg_batch(s2k_engine* e, int32_t* results, 
     if (!nonce_agg_args(who, out_format, pubnonces, nonce_format, nonce_off, n_sessions)) return 0;
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    stream_guard sg(e, e->stream);
     const size_t n = (size_t)nonce_off[n_sessions], nb = musig_nonce_bytes(nonce_format), ob = musig_nonce_bytes(out_format) * n_sessions;
     const agg_sum_plan p = musig_agg_plan_nonces(nonce_off, n_sessions, agg_fanin(e));
     stage_buf b[] = {{nullptr, results, 4 * n_sessions}, {nullptr, aggnonces_out, ob}, {pubnonces, nullptr, nb * n}};
     if (!stage_open(e, b, 0, nonce_agg_ws(p, n))) return 0;
+    stream_guard sg(e, e->stream);
     ws_carver w{e->ws, stage_bytes(b)};
     return stage_close(e, b, nonce_agg_run(e, e->stream, w, p, b[0].at<int32_t>(), b[1].at(), out_format, b[2].at(), nonce_format, n_sessions));
 }
@@ -369,10 +369,10 @@ extern "C" int secp256k1_musig_partial_sig_agg_batch(s2k_engine* e, int32_t* res
     if (!sig_agg_args(who, partial_sigs, sig_format, sig_off, n_sessions)) return 0;
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    stream_guard sg(e, e->stream);
     const size_t n = (size_t)sig_off[n_sessions], sgb = musig_sig_bytes(sig_format), sb = (size_t)MUSIG_SESSION_BYTES * n_sessions;
     stage_buf b[] = {{nullptr, results, 4 * n_sessions}, {nullptr, sigs64_out, 64 * n_sessions}, {sessions133, nullptr, sb}, {partial_sigs, nullptr, sgb * n}};
     if (!stage_open(e, b, 0, 8 * (n_sessions + 1))) return 0;      // (the runner's offsets)
+    stream_guard sg(e, e->stream);
     ws_carver w{e->ws, stage_bytes(b)};
     return stage_close(e, b, sig_agg_run(e, e->stream, w, b[0].at<int32_t>(), b[1].at(), b[2].at(), b[3].at(), sig_format, sig_off, n_sessions));
 }

@@ -1,4 +1,4 @@
-#include "engine_internal.h"
+#include "engine_lanes.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // Borromean rangeproof batch verification (rangeproof.h): five kernels on one stream
@@ -678,7 +678,12 @@ extern "C" int secp256k1_rangeproof_verify_batch_ptrs(s2k_engine* e, int32_t* re
     rp_host_src src{}; src.commit_objs = commit_objs; src.proof_ptrs = proofs; src.plens = plens; src.extra_ptrs = extra; src.elens = elens; src.gen_objs = gen_objs;
     return rp_host_sync(e, who, results, min_value, max_value, src, n);
 }
-// rewind: verification + recovery (rangeproof_rewind.h); host buffers
+// the `_dev` form's workspace, carved from offset 0: outlen when the caller wants no messages, then the replay scratch (ev / prep / secs)
+static size_t rewind_scratch_bytes(const s2k_engine* e, size_t n) {
+    const size_t nw = std::min(n, RP_CHUNK);
+    return ws_need({8 * n, nw * 4096, nw * 4096, nw * 1024});
+}
+// rewind: verification + recovery (rangeproof_rewind.h); host buffers, staged behind the `_dev` form's scratch
 extern "C" int secp256k1_rangeproof_rewind_batch(s2k_engine* e, int32_t* results, unsigned char* blind_out, uint64_t* value_out, unsigned char* message_out,
                                                  uint64_t* outlen, size_t msg_stride, const unsigned char* nonces, uint64_t* min_value, uint64_t* max_value,
                                                  const unsigned char* commits33, const unsigned char* proofs, const uint64_t* proof_off,
@@ -689,40 +694,18 @@ extern "C" int secp256k1_rangeproof_rewind_batch(s2k_engine* e, int32_t* results
         return s2k_fail_arg("secp256k1_rangeproof_rewind_batch", "illegal argument (ARG_CHECK)");
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
-    const size_t pbytes = (size_t)proof_off[n], ebytes = (extra && extra_off) ? (size_t)extra_off[n] : 0;
-    const size_t nw = std::min(n, RP_CHUNK), mbytes = message_out ? msg_stride * n : 0;
-    const size_t io = ws_need({4 * n, 8 * n, 8 * n, 33 * n, pbytes + 64, 8 * (n + 1), ebytes + 64, 8 * (n + 1), 64 * n, 32 * n, 32 * n, 8 * n, 8 * n, mbytes + 64,
-                               nw * 4096, nw * 4096, nw * 1024});
-    if (!engine_workspace(e, io)) return 0;
-    ws_carver c{e->ws, 0}; (void)nw;
-    int32_t* d_res = c.take<int32_t>(n); uint64_t* d_min = c.take<uint64_t>(n); uint64_t* d_max = c.take<uint64_t>(n);
-    unsigned char* d_com = c.take<unsigned char>(33 * n); unsigned char* d_pr = c.take<unsigned char>(pbytes + 64);
-    uint64_t* d_off = c.take<uint64_t>(n + 1); unsigned char* d_ex = c.take<unsigned char>(ebytes + 64); uint64_t* d_eoff = c.take<uint64_t>(n + 1);
-    unsigned char* d_gen = c.take<unsigned char>(64 * n);
-    rp_rewind_args ra;
-    ra.nonces = c.take<unsigned char>(32 * n); ra.blind_out = c.take<unsigned char>(32 * n); ra.value_out = c.take<uint64_t>(n);
-    ra.outlen = c.take<uint64_t>(n); ra.msg_out = message_out ? c.take<unsigned char>(mbytes + 64) : nullptr; ra.msg_stride = msg_stride;
-    ra.ev = c.take<u32>(nw * 1024); ra.prep = c.take<u32>(nw * 1024); ra.secs = c.take<u32>(nw * 256);
-    hipStream_t st = e->stream;
-    stream_guard sg(e, st);
-    HIPCHK(hipMemcpyAsync(d_com, commits33, 33 * n, hipMemcpyHostToDevice, st));
-    if (pbytes) HIPCHK(hipMemcpyAsync(d_pr, proofs, pbytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_off, proof_off, 8 * (n + 1), hipMemcpyHostToDevice, st));
-    if (ebytes) { HIPCHK(hipMemcpyAsync(d_ex, extra, ebytes, hipMemcpyHostToDevice, st)); }
-    if (extra && extra_off) HIPCHK(hipMemcpyAsync(d_eoff, extra_off, 8 * (n + 1), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_gen, gens64, 64 * n, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync((void*)ra.nonces, nonces, 32 * n, hipMemcpyHostToDevice, st));
-    if (message_out) { HIPCHK(hipMemcpyAsync(ra.outlen, outlen, 8 * n, hipMemcpyHostToDevice, st)); HIPCHK(hipMemsetAsync(ra.msg_out, 0, mbytes, st)); }
-    else HIPCHK(hipMemsetAsync(ra.outlen, 0, 8 * n, st));
-    if (!rp_launch(e, st, d_res, d_min, d_max, d_com, d_pr, d_off, (extra && extra_off) ? d_ex : nullptr, (extra && extra_off) ? d_eoff : nullptr, d_gen, n, &ra, 1)) return 0;
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(min_value, d_min, 8 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(max_value, d_max, 8 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(blind_out, ra.blind_out, 32 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(value_out, ra.value_out, 8 * n, hipMemcpyDeviceToHost, st));
-    if (message_out) { HIPCHK(hipMemcpyAsync(message_out, ra.msg_out, mbytes, hipMemcpyDeviceToHost, st)); HIPCHK(hipMemcpyAsync(outlen, ra.outlen, 8 * n, hipMemcpyDeviceToHost, st)); }
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
+    const bool ex = extra && extra_off;
+    const size_t pbytes = (size_t)proof_off[n], ebytes = ex ? (size_t)extra_off[n] : 0, mbytes = message_out ? msg_stride * n : 0;
+    // outlen travels both ways with the messages; without them the `_dev` form takes it from its scratch
+    stage_buf b[] = {{nullptr, results, 4 * n}, {nullptr, min_value, 8 * n}, {nullptr, max_value, 8 * n}, {commits33, nullptr, 33 * n}, {proofs, nullptr, pbytes, 64},
+                     {proof_off, nullptr, 8 * (n + 1)}, {ex ? extra : nullptr, nullptr, ebytes, 64}, {ex ? extra_off : nullptr, nullptr, 8 * (n + 1)}, {gens64, nullptr, 64 * n},
+                     {nonces, nullptr, 32 * n}, {nullptr, blind_out, 32 * n}, {nullptr, value_out, 8 * n},
+                     {message_out ? outlen : nullptr, message_out ? outlen : nullptr, message_out ? 8 * n : 0}, {nullptr, message_out, mbytes, 64}};
+    if (!stage_open(e, b, rewind_scratch_bytes(e, n))) return 0;
+    if (message_out) HIPCHK(hipMemsetAsync(b[13].dev, 0, mbytes, e->stream));
+    return stage_close(e, b, secp256k1_rangeproof_rewind_batch_dev(e, nullptr, b[0].at<int32_t>(), b[10].at(), b[11].at<uint64_t>(), message_out ? b[13].at() : nullptr,
+                                                                   message_out ? b[12].at<uint64_t>() : nullptr, msg_stride, b[9].at(), b[1].at<uint64_t>(), b[2].at<uint64_t>(),
+                                                                   b[3].at(), b[4].at(), b[5].at<uint64_t>(), b[6].opt(), b[7].opt<uint64_t>(), b[8].at(), n));
 }
 // rewind with every array already in HBM (stream-ordered; scratch comes from the engine workspace)
 extern "C" int secp256k1_rangeproof_rewind_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* blind_out, uint64_t* value_out,
@@ -738,7 +721,7 @@ extern "C" int secp256k1_rangeproof_rewind_batch_dev(s2k_engine* e, void* stream
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
     stream_guard sg(e, st);
     const size_t nw = std::min(n, RP_CHUNK);
-    if (!engine_workspace(e, ws_need({8 * n, nw * 4096, nw * 4096, nw * 1024}))) return 0;
+    if (!engine_workspace(e, rewind_scratch_bytes(e, n))) return 0;
     ws_carver c{e->ws, 0};
     rp_rewind_args ra;
     ra.nonces = nonces; ra.blind_out = blind_out; ra.value_out = value_out; ra.msg_out = message_out; ra.msg_stride = msg_stride;
@@ -749,9 +732,6 @@ extern "C" int secp256k1_rangeproof_rewind_batch_dev(s2k_engine* e, void* stream
     // -- on the side stream, so that stream has to wait for whatever an earlier call queued on `st` may still be doing with the workspace
     return rp_launch(e, st, results, min_value, max_value, commits33, proofs, proof_off, extra, extra_off, gens64, n, &ra, 1);
 }
-// single-item forms with the reference's argument lists.  A 0 from these means "invalid" only while s2k_last_status() is
-// S2K_STATUS_OK; an engine-level failure also returns 0 (never 1) and leaves S2K_STATUS_ENGINE_FAILURE for the caller's
-// CPU fallback (integration/secp256k1_amd_hook.c does exactly that).
 // ------------------------------------------------------------------------------------------------------------
 // surjection-proof batch verification (surjection.h): one proof per lane
 // ------------------------------------------------------------------------------------------------------------
@@ -773,22 +753,10 @@ extern "C" int secp256k1_surjectionproof_verify_batch_dev(s2k_engine* e, void* s
                                                           const unsigned char* output_tags64, size_t n) {
     if (!e) return s2k_fail("secp256k1_surjectionproof_verify_batch_dev", "null engine");
     if (n == 0) return 1;
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::recursive_mutex> lock(e->mu);
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    stream_guard sg(e, st);
-    if (!engine_ptab(e, ((std::min(n, e->max_lanes) + 255) / 256) * 256)) return 0;
-    ENGINE_GTAB(e, st);
-    HIPCHK(hipMemsetAsync(results, 0, sizeof(int32_t) * n, st));          // a batch that does not complete never shows an item as valid
-    HIPCHK(hipEventRecord(e->ev[0], st)); HIPCHK(hipEventRecord(e->ev[2], st));
-    for (size_t i0 = 0; i0 < n; i0 += e->max_lanes) {     // offsets are absolute, so a sub-range only shifts the per-item arrays
-        const size_t m = std::min(n - i0, e->max_lanes);
-        hipLaunchKernelGGL(k_sj_verify, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, results + i0, proofs, proof_off + i0, input_tags64, tag_off + i0,
-                           output_tags64 + 64 * i0, e->gtab, e->ptab, m);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e->ev[3], st)); HIPCHK(hipEventRecord(e->ev[1], st));
-    return 1;
+    return lanes_run(e, stream, n, {true, true, 0}, {{results, 4 * n}},                       // a batch that does not complete never shows an item as valid
+                     [&](size_t i0, size_t m, dim3 grid, hipStream_t st, u32*) {              // offsets are absolute, so a sub-range only shifts the per-item arrays
+        hipLaunchKernelGGL(k_sj_verify, grid, dim3(256), 0, st, results + i0, proofs, proof_off + i0, input_tags64, tag_off + i0, output_tags64 + 64 * i0, e->gtab, e->ptab, m);
+    });
 }
 extern "C" int secp256k1_surjectionproof_verify_batch(s2k_engine* e, int32_t* results, const unsigned char* proofs, const uint64_t* proof_off,
                                                       const unsigned char* input_tags64, const uint64_t* tag_off, const unsigned char* output_tags64, size_t n) {
@@ -798,21 +766,10 @@ extern "C" int secp256k1_surjectionproof_verify_batch(s2k_engine* e, int32_t* re
     std::lock_guard<std::recursive_mutex> lock(e->mu);
     HIPCHK(hipSetDevice(e->device));
     const size_t pbytes = (size_t)proof_off[n], ntags = (size_t)tag_off[n];
-    if (!engine_workspace(e, ws_need({4 * n, pbytes + 64, 8 * (n + 1), 64 * ntags + 64, 8 * (n + 1), 64 * n}))) return 0;
-    ws_carver w{e->ws, 0};
-    int32_t* d_res = w.take<int32_t>(n); unsigned char* d_pr = w.take<unsigned char>(pbytes + 64); uint64_t* d_po = w.take<uint64_t>(n + 1);
-    unsigned char* d_in = w.take<unsigned char>(64 * ntags + 64); uint64_t* d_to = w.take<uint64_t>(n + 1); unsigned char* d_out = w.take<unsigned char>(64 * n);
-    hipStream_t st = e->stream;
-    stream_guard sg(e, st);
-    if (pbytes) HIPCHK(hipMemcpyAsync(d_pr, proofs, pbytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_po, proof_off, 8 * (n + 1), hipMemcpyHostToDevice, st));
-    if (ntags) HIPCHK(hipMemcpyAsync(d_in, input_tags64, 64 * ntags, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_to, tag_off, 8 * (n + 1), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_out, output_tags64, 64 * n, hipMemcpyHostToDevice, st));
-    if (!secp256k1_surjectionproof_verify_batch_dev(e, nullptr, d_res, d_pr, d_po, d_in, d_to, d_out, n)) return 0;
-    HIPCHK(hipMemcpyAsync(results, d_res, 4 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
+    stage_buf b[] = {{nullptr, results, 4 * n}, {proofs, nullptr, pbytes, 64}, {proof_off, nullptr, 8 * (n + 1)}, {input_tags64, nullptr, 64 * ntags, 64},
+                     {tag_off, nullptr, 8 * (n + 1)}, {output_tags64, nullptr, 64 * n}};
+    if (!stage_open(e, b)) return 0;
+    return stage_close(e, b, secp256k1_surjectionproof_verify_batch_dev(e, nullptr, b[0].at<int32_t>(), b[1].at(), b[2].at<uint64_t>(), b[3].at(), b[4].at<uint64_t>(), b[5].at(), n));
 }
 #ifdef S2K_PROF
 // diagnostic builds only: read (and clear) the per-region cycle table of s2k_common.h.  Every translation unit has its own copy of the

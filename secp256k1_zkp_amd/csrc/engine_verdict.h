@@ -89,8 +89,8 @@ static int verdict_host(s2k_engine* e, const stage_buf (&in)[N], size_t front, i
     b[N] = stage_buf{nullptr, nullptr, 4 * n, 64}; b[N + 1] = stage_buf{nullptr, seed32_out, 32, 32}; b[N + 2] = stage_buf{nullptr, verdict, 4, 12};
     hipStream_t st = e->stream;
     {
-        stream_guard sg(e, st);
         if (!stage_open(e, b, front)) return 0;
+        stream_guard sg(e, st);
         ws_carver c{e->ws, 0};
         if (!stage_close(e, b, launch(st, c, (int32_t*)b[N + 2].dev, seed32_out ? b[N + 1].dev : nullptr, (const stage_buf*)b))) return 0;
     }

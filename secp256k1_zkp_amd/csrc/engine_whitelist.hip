@@ -135,9 +135,9 @@ extern "C" int secp256k1_whitelist_verify_batch(s2k_engine* e, int32_t* results,
     // the items' bytes [sig_off[0], sig_off[n]) go to HBM as they are, with offsets relative to their start; every list is uploaded once
     const size_t sig_lo = (size_t)sig_off[0], sig_bytes = (size_t)(sig_off[n] - sig_off[0]), key_bytes = 64 * (size_t)list_off[n_lists];
     hipStream_t st = e->stream;
-    stream_guard sg(e, st);
     stage_buf b[] = {{nullptr, results, 4 * n}, {sigs + sig_lo, nullptr, sig_bytes, 64}, {online64, nullptr, key_bytes, 64}, {offline64, nullptr, key_bytes, 64}, {sub64, nullptr, 64 * n}};
     if (!stage_open(e, b, 0, wl_ws_bytes(n, n_lists, wl_pairs(sig_off, list_off, list_of, n)))) return 0;
+    stream_guard sg(e, st);
     std::vector<uint64_t> rel(n + 1);
     for (size_t i = 0; i <= n; i++) rel[i] = sig_off[i] - sig_lo;
     HIPCHK(hipMemsetAsync(b[0].dev, 0, sizeof(int32_t) * n, st));
