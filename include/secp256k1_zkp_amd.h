@@ -83,6 +83,9 @@ S2K_API void s2k_clear_status(void);
  * S2K_OPT_S2C_FUSED (default 0): secp256k1_anti_exfil_host_verify_batch runs the commitment check and the ECDSA verification in one kernel
  *   instead of the default chain of two (the commitment kernel's verdicts into a byte array, then an ECDSA kernel that ANDs them in).
  *   Results do not depend on it; the chain is the default because it measured faster (tools/s2c_bare.py).
+ * S2K_OPT_PUBKEY_FOLD_FANIN (default 16, 2..64): how many keys one lane of the first pass of secp256k1_ec_pubkey_combine_batch folds, and
+ *   how many partial sums one lane of its further passes folds.  Every value gives the same results (S2K_OPT_MUSIG_SUM_FANIN does not
+ *   touch this call).
  * S2K_OPT_ELLSWIFT_MAX_ATTEMPTS (default and maximum 256, minimum 1): the bound of the rejection loop of secp256k1_ellswift_encode_batch.  An item
  *   that finds no encoding within it gets results[i] = 0 and zero bytes and is counted (s2k_engine_ellswift_capped); at the default this is out
  *   of reach of any input (about 1e-32 per item).  Smaller values exist for tests of the cap; the bytes of an item that succeeds do not depend on it.
@@ -102,6 +105,7 @@ S2K_API void s2k_clear_status(void);
 #define S2K_OPT_MUSIG_SUM_FANIN 12
 #define S2K_OPT_S2C_FUSED 13
 #define S2K_OPT_ELLSWIFT_MAX_ATTEMPTS 14
+#define S2K_OPT_PUBKEY_FOLD_FANIN 15
 S2K_API int s2k_engine_set_option(s2k_engine* e, int option, long value);
 /* Rangeproof generator tables.  The four public keys of a Borromean ring differ by multiples of the proof's generator
  * (secp256k1_rangeproof_pub_expand, src/modules/rangeproof/rangeproof_impl.h:19-51), so when the engine holds a fixed-base table of that
@@ -461,6 +465,71 @@ S2K_API int secp256k1_pubkey_tweak_add_batch(s2k_engine* e, int32_t* results, un
 S2K_API int secp256k1_pubkey_tweak_add_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* pubkeys_out64, const unsigned char* keys,
                                                  int key_format, const unsigned char* tweaks32, size_t n);
 
+/* ---- public keys: conversion between encodings, negation, tweak-mul, combine ---------------------------------------------
+ * PUBLIC INPUTS ONLY: nothing below is constant time.  The engine uses five encodings of a curve point; these calls move a batch
+ * from any of them to any other without leaving HBM, and serve the public-key group of include/secp256k1.h.
+ *   S2K_PK_XONLY        32 bytes   in: as secp256k1_xonly_pubkey_parse (src/modules/extrakeys/main_impl.h:22-42: x >= p or x not on
+ *                                  the curve gives 0; the even y).  out: ser32(x) (secp256k1_xonly_pubkey_serialize behind
+ *                                  secp256k1_xonly_pubkey_from_pubkey, :44-59, :85-116)
+ *   S2K_PK_OBJECT       64 bytes   the opaque `secp256k1_pubkey` / `secp256k1_xonly_pubkey` object.  in: read as it is
+ *                                  (secp256k1_pubkey_load; an odd y stays odd).  out: byte for byte what secp256k1_pubkey_save writes
+ *   S2K_PK_COMPRESSED   33 bytes   in: secp256k1_ec_pubkey_parse, 33-byte case (src/secp256k1.c:290-306, src/eckey_impl.h:18-36).
+ *                                  out: secp256k1_ec_pubkey_serialize(.., SECP256K1_EC_COMPRESSED) (secp256k1.c:308-332)
+ *   S2K_PK_FULL         65 bytes   in: secp256k1_ec_pubkey_parse, 65-byte case: prefixes 04 / 06 / 07 with the hybrid parity rule.
+ *                                  out: prefix 04 (SECP256K1_EC_UNCOMPRESSED)
+ *   S2K_PK_AFFINE       64 bytes   x | y big-endian: a_xy / pt_xy / r_xy of s2k_ecmult_batch, s2k_ecmult2_batch, s2k_ecmult_multi*.
+ *                                  in: accepted iff x < p, y < p and the point is on the curve.  out: x | y
+ *   S2K_PK_XONLY_OBJECT 64 bytes   OUTPUT ONLY (as input it is S2K_PK_OBJECT): the object with y made even
+ *                                  (secp256k1_xonly_pubkey_from_pubkey)
+ * (0, 1 and 2 are the key_format numbers of the tweak calls above.)  Formats 0 and 2 cost a square root per key on the way in, 3 and 4
+ * an on-curve check, 1 nothing.
+ * Common to every call: results[i] is the reference's return value; where it is 0 the item's output bytes are all zero.  parities_out
+ * (n bytes, may be NULL) receives is_odd(y) of the result point -- for the two x-only output formats that is the parity the encoding
+ * drops, the pk_parity of secp256k1_xonly_pubkey_from_pubkey -- and 0 where the item is refused.  n == 0 returns 1; NULL where the
+ * reference has ARG_CHECK or a format out of range is S2K_STATUS_ILLEGAL_ARGUMENT (return 0).  The host forms zero results and the
+ * outputs before anything can fail; the _dev forms (every array in HBM) zero them on the stream first.
+ * DIFFERENCES FROM THE REFERENCE: S2K_PK_AFFINE is defined here (the reference has no such call); a refused item's output is zero
+ * bytes in EVERY output format (the reference's serialisers leave their buffer's tail as it was); an object whose x is all zero,
+ * where the reference calls its illegal-argument callback, gives 0.
+ *
+ * convert:   out_i = in_i in another encoding.  By choice of formats: secp256k1_ec_pubkey_parse (2 or 3 -> 1),
+ *            secp256k1_ec_pubkey_serialize (1 -> 2 or 3), secp256k1_xonly_pubkey_parse (0 -> 1), secp256k1_xonly_pubkey_serialize
+ *            (1 -> 0), secp256k1_xonly_pubkey_from_pubkey (1 -> 5, with parities_out), and the bridge to and from x | y (4).
+ * negate:    the same with y negated before the store (secp256k1_ec_pubkey_negate, secp256k1.c:723-736). */
+#define S2K_PK_XONLY 0
+#define S2K_PK_OBJECT 1
+#define S2K_PK_COMPRESSED 2
+#define S2K_PK_FULL 3
+#define S2K_PK_AFFINE 4
+#define S2K_PK_XONLY_OBJECT 5
+S2K_API int secp256k1_ec_pubkey_convert_batch(s2k_engine* e, int32_t* results, unsigned char* out, int out_format, unsigned char* parities_out,
+                                              const unsigned char* in, int in_format, size_t n);
+S2K_API int secp256k1_ec_pubkey_convert_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* out, int out_format, unsigned char* parities_out,
+                                                  const unsigned char* in, int in_format, size_t n);
+S2K_API int secp256k1_ec_pubkey_negate_batch(s2k_engine* e, int32_t* results, unsigned char* out, int out_format, unsigned char* parities_out,
+                                             const unsigned char* in, int in_format, size_t n);
+S2K_API int secp256k1_ec_pubkey_negate_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* out, int out_format, unsigned char* parities_out,
+                                                 const unsigned char* in, int in_format, size_t n);
+/* tweak-mul: results[i] = secp256k1_ec_pubkey_tweak_mul(ctx, key_i -> out_i, tweak32_i)      (secp256k1.c:810-831, eckey_impl.h:82-92)
+ * 0 for a tweak >= the group order, a tweak of 0 and a key that does not load; otherwise out_i = t_i * P_i, which is never infinite.
+ * tweaks32 n*32 big-endian.  One variable-point multiplication per item: the cost of s2k_ecmult_batch with ng == NULL. */
+S2K_API int secp256k1_ec_pubkey_tweak_mul_batch(s2k_engine* e, int32_t* results, unsigned char* out, int out_format, unsigned char* parities_out,
+                                                const unsigned char* keys, int key_format, const unsigned char* tweaks32, size_t n);
+S2K_API int secp256k1_ec_pubkey_tweak_mul_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* out, int out_format, unsigned char* parities_out,
+                                                    const unsigned char* keys, int key_format, const unsigned char* tweaks32, size_t n);
+/* combine: results[k] = secp256k1_ec_pubkey_combine(ctx, out_k, the keys of set k, their count)      (secp256k1.c:843-867)
+ * keys: the keys of all sets, concatenated; set k owns keys [key_off[k], key_off[k+1]).  key_off has n_sets + 1 entries, starts at 0,
+ * never decreases and is a HOST array in both forms, read before the call returns.  0 for an empty set (ARG_CHECK(n >= 1)), a set with a
+ * key that does not load (DIFFERENCE: the reference ignores secp256k1_pubkey_load's verdict there after its callback) and a sum at
+ * infinity; otherwise the sum.  A launch chain planned from the offsets: a first pass in which one lane folds up to F consecutive keys
+ * of one set straight from their bytes (S2K_OPT_PUBKEY_FOLD_FANIN), further passes only while a set has more than one partial sum, one
+ * to-affine step per set.  Keys in formats 0 and 2 cost a square root EACH (they are first loaded one key per lane, so that the roots
+ * run side by side, and then summed): S2K_PK_OBJECT and S2K_PK_AFFINE are the fast path. */
+S2K_API int secp256k1_ec_pubkey_combine_batch(s2k_engine* e, int32_t* results, unsigned char* out, int out_format, unsigned char* parities_out,
+                                              const unsigned char* keys, int key_format, const uint64_t* key_off, size_t n_sets);
+S2K_API int secp256k1_ec_pubkey_combine_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* out, int out_format, unsigned char* parities_out,
+                                                  const unsigned char* keys, int key_format, const uint64_t* key_off_host, size_t n_sets);
+
 /* ---- asset generators ----------------------------------------------------------------------------------------------
  * PUBLIC INPUTS ONLY: nothing below is constant time.  A blind handed to these functions is treated as public data (the
  * reference's generate_blinded and pedersen_commit are secret-key paths; here they serve explicit amounts, blind 0, and the
@@ -738,6 +807,25 @@ S2K_API int secp256k1_xonly_pubkey_tweak_add_check_amd(const void* ctx, const un
                                                        const void* internal_pubkey, const unsigned char* tweak32);
 S2K_API int secp256k1_xonly_pubkey_tweak_add_amd(const void* ctx, void* output_pubkey, const void* internal_pubkey, const unsigned char* tweak32);
 S2K_API int secp256k1_ec_pubkey_tweak_add_amd(const void* ctx, void* pubkey, const unsigned char* tweak32);
+/*   secp256k1_ec_pubkey_parse(ctx, pubkey, input, inputlen)                          src/secp256k1.c:290
+ *   secp256k1_ec_pubkey_serialize(ctx, output, outputlen, pubkey, flags)             src/secp256k1.c:308
+ *   secp256k1_ec_pubkey_negate(ctx, pubkey)                                          src/secp256k1.c:723
+ *   secp256k1_ec_pubkey_tweak_mul(ctx, pubkey, tweak32)                              src/secp256k1.c:810
+ *   secp256k1_ec_pubkey_combine(ctx, out, ins, n)                                    src/secp256k1.c:843
+ *   secp256k1_xonly_pubkey_parse(ctx, pubkey, input32)                               src/modules/extrakeys/main_impl.h:22
+ *   secp256k1_xonly_pubkey_serialize(ctx, output32, pubkey)                          src/modules/extrakeys/main_impl.h:44
+ *   secp256k1_xonly_pubkey_from_pubkey(ctx, xonly_pubkey, pk_parity, pubkey)         src/modules/extrakeys/main_impl.h:85
+ * pubkey / xonly_pubkey / out: 64-byte objects, zeroed first wherever the reference does; an inputlen other than 33 or 65 gives 0
+ * without a launch; flags: SECP256K1_EC_COMPRESSED (258) or SECP256K1_EC_UNCOMPRESSED (2), *outputlen in: the buffer's size, out:
+ * 33 / 65 (0 on failure); ins: n pointers to objects; pk_parity may be NULL. */
+S2K_API int secp256k1_ec_pubkey_parse_amd(const void* ctx, void* pubkey, const unsigned char* input, size_t inputlen);
+S2K_API int secp256k1_ec_pubkey_serialize_amd(const void* ctx, unsigned char* output, size_t* outputlen, const void* pubkey, unsigned int flags);
+S2K_API int secp256k1_ec_pubkey_negate_amd(const void* ctx, void* pubkey);
+S2K_API int secp256k1_ec_pubkey_tweak_mul_amd(const void* ctx, void* pubkey, const unsigned char* tweak32);
+S2K_API int secp256k1_ec_pubkey_combine_amd(const void* ctx, void* out, const void* const* ins, size_t n);
+S2K_API int secp256k1_xonly_pubkey_parse_amd(const void* ctx, void* pubkey, const unsigned char* input32);
+S2K_API int secp256k1_xonly_pubkey_serialize_amd(const void* ctx, unsigned char* output32, const void* pubkey);
+S2K_API int secp256k1_xonly_pubkey_from_pubkey_amd(const void* ctx, void* xonly_pubkey, int* pk_parity, const void* pubkey);
 /*   secp256k1_generator_generate(ctx, gen, key32)                                  src/modules/generator/main_impl.h:250
  *   secp256k1_generator_parse(ctx, gen, input)                                     src/modules/generator/main_impl.h:59
  *   secp256k1_pedersen_commit(ctx, commit, blind, value, gen)                      src/modules/generator/main_impl.h:309
@@ -915,6 +1003,8 @@ S2K_API int secp256k1_musig_partial_sig_verify_batch_group(s2k_group* g, int32_t
                                                            const uint32_t* session_of, size_t n);
 S2K_API int secp256k1_xonly_pubkey_tweak_add_check_batch_group(s2k_group* g, int32_t* results, const unsigned char* tweaked32, const unsigned char* parities,
                                                                const unsigned char* internal_keys, int key_format, const unsigned char* tweaks32, size_t n);
+S2K_API int secp256k1_ec_pubkey_tweak_mul_batch_group(s2k_group* g, int32_t* results, unsigned char* out, int out_format, unsigned char* parities_out,
+                                                      const unsigned char* keys, int key_format, const unsigned char* tweaks32, size_t n);
 S2K_API int s2k_ecmult_multi_group(s2k_group* g, unsigned char* r_xy, int32_t* r_inf, const unsigned char* g_sc, const unsigned char* sc,
                                    const unsigned char* pt_xy, const unsigned char* pt_inf, size_t n);
 S2K_API int s2k_ecmult_multi_group_dev(s2k_group* g, unsigned char* r_xy, int32_t* r_inf, const unsigned char* g_sc_dev0,

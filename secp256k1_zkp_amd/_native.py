@@ -72,6 +72,23 @@ SIGNATURES = {
     "secp256k1_xonly_pubkey_tweak_add_check_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "secp256k1_pubkey_tweak_add_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
     "secp256k1_pubkey_tweak_add_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_ec_pubkey_convert_batch": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_ec_pubkey_convert_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_ec_pubkey_negate_batch": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_ec_pubkey_negate_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_ec_pubkey_tweak_mul_batch": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_ec_pubkey_tweak_mul_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_ec_pubkey_tweak_mul_batch_group": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_ec_pubkey_combine_batch": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_ec_pubkey_combine_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _c.c_int, _vp, _sz]),
+    "secp256k1_ec_pubkey_parse_amd": (_c.c_int, [_vp, _vp, _vp, _sz]),
+    "secp256k1_ec_pubkey_serialize_amd": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_uint]),
+    "secp256k1_ec_pubkey_negate_amd": (_c.c_int, [_vp, _vp]),
+    "secp256k1_ec_pubkey_tweak_mul_amd": (_c.c_int, [_vp, _vp, _vp]),
+    "secp256k1_ec_pubkey_combine_amd": (_c.c_int, [_vp, _vp, _vp, _sz]),
+    "secp256k1_xonly_pubkey_parse_amd": (_c.c_int, [_vp, _vp, _vp]),
+    "secp256k1_xonly_pubkey_serialize_amd": (_c.c_int, [_vp, _vp, _vp]),
+    "secp256k1_xonly_pubkey_from_pubkey_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "secp256k1_generator_generate_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "secp256k1_generator_generate_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "secp256k1_generator_parse_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _sz]),

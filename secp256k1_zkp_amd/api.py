@@ -159,6 +159,26 @@ def _tweak_check_args(what, tweaked32, parities, internal_keys, tweaks32, key_fo
     return tweaked32, parities, internal_keys, tweaks32, n
 
 
+_PK_BYTES = {0: 32, 1: 64, 2: 33, 3: 65, 4: 64, 5: 64}     # include/secp256k1_zkp_amd.h: S2K_PK_*; 5 (x-only object) is an output format only
+
+
+def _pk_formats(what, out_format, in_format):
+    if out_format not in _PK_BYTES:
+        raise ValueError(f"{what}: out_format must be 0 .. 5 (S2K_PK_*)")
+    if in_format not in _PK_BYTES or in_format == 5:
+        raise ValueError(f"{what}: the input format must be 0 .. 4 (S2K_PK_*; 5 is an output format)")
+
+
+def _pk_tweak_mul_args(what, keys, key_format, tweaks32, out_format):
+    """shape checks shared by Engine.pubkey_tweak_mul and Group.pubkey_tweak_mul"""
+    _pk_formats(what, out_format, key_format)
+    if keys is None or tweaks32 is None:
+        raise ValueError(f"{what}: missing array")
+    keys = _u8(keys); tweaks32 = _u8(tweaks32); n = tweaks32.size // 32
+    _need(what + " tweaks32", tweaks32, 32 * n); _need(what + " keys", keys, _PK_BYTES[key_format] * n)
+    return keys, tweaks32, n
+
+
 class Engine:
     """One engine per GPU/process (owns a stream, the generator table and an HBM workspace)."""
 
@@ -201,6 +221,7 @@ class Engine:
     OPT_MUSIG_SUM_FANIN = 12
     OPT_S2C_FUSED = 13
     OPT_ELLSWIFT_MAX_ATTEMPTS = 14
+    OPT_PUBKEY_FOLD_FANIN = 15
 
     def cache_generator(self, gen64):
         """Build the fixed-base table of one rangeproof generator now (s2k_engine_cache_generator)."""
@@ -637,6 +658,76 @@ class Engine:
         n = tweaks32.numel() // 32 if n is None else n
         self._check(self._lib.secp256k1_pubkey_tweak_add_batch_dev(self._h, stream, _dp(results), _dp(pubkeys_out64), _dp(keys), key_format, _dp(tweaks32), n),
                     "secp256k1_pubkey_tweak_add_batch_dev")
+
+    # ---- the public-key group of include/secp256k1.h and secp256k1_extrakeys.h: conversion, negation, tweak-mul, combine (csrc/pubkey.h), batched ----
+    def _pk_convert(self, what, keys, in_format, out_format):
+        _pk_formats(what, out_format, in_format)
+        if keys is None:
+            raise ValueError(f"{what}: missing array")
+        keys = _u8(keys); n = keys.size // _PK_BYTES[in_format]
+        _need(what + " keys", keys, _PK_BYTES[in_format] * n)
+        res = np.zeros(n, np.int32); out = np.zeros((n, _PK_BYTES[out_format]), np.uint8); par = np.zeros(n, np.uint8)
+        self._check(getattr(self._lib, what)(self._h, _p(res), _p(out), out_format, _p(par), _p(keys), in_format, n), what)
+        return res, out, par
+
+    def pubkey_convert(self, keys, in_format, out_format):
+        """keys: n keys in in_format (S2K_PK_*: 0 x-only 32 bytes, 1 object 64, 2 compressed 33, 3 uncompressed / hybrid 65, 4 x | y 64)
+        -> (results[n], out[n, bytes of out_format], parities[n]); out_format also 5: the object with y made even.  A refused key's output is zero."""
+        return self._pk_convert("secp256k1_ec_pubkey_convert_batch", keys, in_format, out_format)
+
+    def pubkey_convert_dev(self, results, out, keys, in_format, out_format, parities_out=None, n=None, stream=None):
+        """every array in HBM (torch tensors); parities_out may be None"""
+        _pk_formats("pubkey_convert_dev", out_format, in_format)
+        n = keys.numel() // _PK_BYTES[in_format] if n is None else n
+        self._check(self._lib.secp256k1_ec_pubkey_convert_batch_dev(self._h, stream, _dp(results), _dp(out), out_format, _dp(parities_out), _dp(keys), in_format, n),
+                    "secp256k1_ec_pubkey_convert_batch_dev")
+
+    def pubkey_negate(self, keys, in_format, out_format):
+        """as pubkey_convert, with every key negated (secp256k1_ec_pubkey_negate)"""
+        return self._pk_convert("secp256k1_ec_pubkey_negate_batch", keys, in_format, out_format)
+
+    def pubkey_negate_dev(self, results, out, keys, in_format, out_format, parities_out=None, n=None, stream=None):
+        _pk_formats("pubkey_negate_dev", out_format, in_format)
+        n = keys.numel() // _PK_BYTES[in_format] if n is None else n
+        self._check(self._lib.secp256k1_ec_pubkey_negate_batch_dev(self._h, stream, _dp(results), _dp(out), out_format, _dp(parities_out), _dp(keys), in_format, n),
+                    "secp256k1_ec_pubkey_negate_batch_dev")
+
+    def pubkey_tweak_mul(self, keys, tweaks32, key_format=1, out_format=1):
+        """results[i] = secp256k1_ec_pubkey_tweak_mul(key_i, tweak32_i) -> (results[n], out[n, bytes of out_format], parities[n]);
+        0 and zero bytes for a tweak >= the group order, a tweak of 0 and a key that does not load"""
+        keys, tweaks32, n = _pk_tweak_mul_args("pubkey_tweak_mul", keys, key_format, tweaks32, out_format)
+        res = np.zeros(n, np.int32); out = np.zeros((n, _PK_BYTES[out_format]), np.uint8); par = np.zeros(n, np.uint8)
+        self._check(self._lib.secp256k1_ec_pubkey_tweak_mul_batch(self._h, _p(res), _p(out), out_format, _p(par), _p(keys), key_format, _p(tweaks32), n),
+                    "secp256k1_ec_pubkey_tweak_mul_batch")
+        return res, out, par
+
+    def pubkey_tweak_mul_dev(self, results, out, keys, tweaks32, key_format=1, out_format=1, parities_out=None, n=None, stream=None):
+        _pk_formats("pubkey_tweak_mul_dev", out_format, key_format)
+        n = tweaks32.numel() // 32 if n is None else n
+        self._check(self._lib.secp256k1_ec_pubkey_tweak_mul_batch_dev(self._h, stream, _dp(results), _dp(out), out_format, _dp(parities_out), _dp(keys), key_format,
+                                                                      _dp(tweaks32), n), "secp256k1_ec_pubkey_tweak_mul_batch_dev")
+
+    def pubkey_combine(self, keys, key_off, key_format=1, out_format=1):
+        """keys: the keys of all sets, concatenated; set k owns keys [key_off[k], key_off[k+1]) (n_sets + 1 entries, starting at 0, never
+        decreasing).  -> (results[n_sets], out[n_sets, bytes of out_format], parities[n_sets]): secp256k1_ec_pubkey_combine per set; 0 and
+        zero bytes for an empty set, a set with a key that does not load and a sum at infinity.  Formats 1 and 4 are the fast path."""
+        _pk_formats("pubkey_combine", out_format, key_format)
+        if keys is None:
+            raise ValueError("pubkey_combine: missing array")
+        keys = _u8(keys)
+        key_off = self._musig_off("pubkey_combine", key_off, _PK_BYTES[key_format], keys)
+        n = key_off.size - 1
+        res = np.zeros(n, np.int32); out = np.zeros((n, _PK_BYTES[out_format]), np.uint8); par = np.zeros(n, np.uint8)
+        self._check(self._lib.secp256k1_ec_pubkey_combine_batch(self._h, _p(res), _p(out), out_format, _p(par), _p(keys), key_format, _p(key_off), n),
+                    "secp256k1_ec_pubkey_combine_batch")
+        return res, out, par
+
+    def pubkey_combine_dev(self, results, out, keys, key_off, key_format=1, out_format=1, parities_out=None, stream=None):
+        """byte arrays in HBM (torch tensors); key_off is a HOST array of n_sets + 1 key counts, read before the call returns"""
+        _pk_formats("pubkey_combine_dev", out_format, key_format)
+        key_off = self._musig_off("pubkey_combine_dev", key_off, 0, None)
+        self._check(self._lib.secp256k1_ec_pubkey_combine_batch_dev(self._h, stream, _dp(results), _dp(out), out_format, _dp(parities_out), _dp(keys), key_format, _p(key_off),
+                                                                    key_off.size - 1), "secp256k1_ec_pubkey_combine_batch_dev")
 
     # ---- secp256k1_ellswift_decode and secp256k1_ellswift_encode (modules/ellswift/main_impl.h:470-483, :393-420), batched ----
     def ellswift_decode(self, ell64, out_format=1):
@@ -1195,6 +1286,14 @@ class Group:
         self._check(self._lib.secp256k1_xonly_pubkey_tweak_add_check_batch_group(self._h, _p(res), _p(tweaked32), _p(parities), _p(internal_keys), key_format,
                                                                                   _p(tweaks32), n), "secp256k1_xonly_pubkey_tweak_add_check_batch_group")
         return res
+
+    def pubkey_tweak_mul(self, keys, tweaks32, key_format=1, out_format=1):
+        """Engine.pubkey_tweak_mul with the items shared out over the group's engines"""
+        keys, tweaks32, n = _pk_tweak_mul_args("Group.pubkey_tweak_mul", keys, key_format, tweaks32, out_format)
+        res = np.zeros(n, np.int32); out = np.zeros((n, _PK_BYTES[out_format]), np.uint8); par = np.zeros(n, np.uint8)
+        self._check(self._lib.secp256k1_ec_pubkey_tweak_mul_batch_group(self._h, _p(res), _p(out), out_format, _p(par), _p(keys), key_format, _p(tweaks32), n),
+                    "secp256k1_ec_pubkey_tweak_mul_batch_group")
+        return res, out, par
 
     def ecmult_multi(self, sc, pt_xy, g_sc=None, pt_inf=None):
         sc = _u8(sc); pt_xy = _u8(pt_xy); n = sc.size // 32

@@ -2,6 +2,7 @@
 #include "s2c.h"         // the per-format item sizes the `_group` forms split by: ecdsa.h, tweak.h (both through s2c.h), s2c.h, ellswift.h, musig.h
 #include "ellswift.h"
 #include "musig.h"
+#include "pubkey.h"      // pubkey_bytes
 
 // ------------------------------------------------------------------------------------------------------------
 // error plumbing
@@ -461,7 +462,7 @@ extern "C" s2k_engine* s2k_engine_create(int device) {
     for (int i = 0; i < 2; i++) { auto& m = e->msm_slot[i]; m.s = m.s2 = nullptr; m.fork = m.join = m.done = m.in = nullptr; m.ws = nullptr; m.ws_bytes = 0; m.seen_epoch = 0; }
     e->msm_seq = 0; e->cur_pipe = 0; e->ev_last_np = nullptr; e->np_epoch = 0; e->np_valid = 0;
     e->msm_pipeline = 0; e->halfagg_host_chain = 1; e->sync_split = 1; e->stage_log = 0;
-    e->msm_diag = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; e->msm_max_terms_opt = 0; e->musig_sum_fanin = 0; e->s2c_fused = 0; e->ellswift_max_attempts = 256;
+    e->msm_diag = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; e->msm_max_terms_opt = 0; e->musig_sum_fanin = 0; e->pubkey_fold_fanin = 0; e->s2c_fused = 0; e->ellswift_max_attempts = 256;
     for (int i = 0; i < 2; i++) { e->rp_mem[i] = nullptr; e->ev_rp_fork[i] = e->ev_rp_join[i] = e->ev_rp_pre[i] = e->ev_rp_done[i] = nullptr; e->rp_done_valid[i] = 0; }
     e->rp_debug = 0;
     for (int i = 0; i < 2; i++) { auto& S = e->stage[i]; S.in = S.out = S.dev = nullptr; S.in_bytes = S.out_bytes = S.dev_bytes = 0; S.ev_h2d = S.ev_out = nullptr; S.used = 0; S.ticket = 0; S.sync_owned = 0; }
@@ -907,6 +908,87 @@ extern "C" int secp256k1_ec_pubkey_tweak_add_amd(const void* ctx, void* pubkey, 
         return secp256k1_pubkey_tweak_add_batch(e, res, (unsigned char*)pubkey, in, 1, tweak32, 1);
     });
 }
+// include/secp256k1.h and include/secp256k1_extrakeys.h: the public-key group (the kernels live in engine_pubkey.hip).  Objects are 64 bytes.
+// src/secp256k1.c:290 -- the object is zeroed first; a length that is neither 33 nor 65 parses as 0 (eckey_impl.h:18-36)
+extern "C" int secp256k1_ec_pubkey_parse_amd(const void* ctx, void* pubkey, const unsigned char* input, size_t inputlen) {
+    (void)ctx;
+    if (!amd_args("secp256k1_ec_pubkey_parse_amd", pubkey != nullptr, pubkey, 64, input != nullptr)) return 0;
+    if (inputlen != 33 && inputlen != 65) return 0;
+    return amd_call(pubkey, 64, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_ec_pubkey_convert_batch(e, res, (unsigned char*)pubkey, S2K_PK_OBJECT, nullptr, input, inputlen == 33 ? S2K_PK_COMPRESSED : S2K_PK_FULL, 1);
+    });
+}
+// src/secp256k1.c:308 -- the checks in the reference's order: outputlen, its value, (*outputlen = 0), output (zeroed over its whole length), pubkey, flags
+extern "C" int secp256k1_ec_pubkey_serialize_amd(const void* ctx, unsigned char* output, size_t* outputlen, const void* pubkey, unsigned int flags) {
+    (void)ctx;
+    const char* who = "secp256k1_ec_pubkey_serialize_amd";
+    const bool compressed = (flags & (1u << 8)) != 0;
+    if (!amd_args(who, outputlen && *outputlen >= (compressed ? 33u : 65u))) return 0;
+    const size_t len = *outputlen;
+    *outputlen = 0;
+    if (!amd_args(who, output != nullptr, output, len, pubkey && (flags & 0xFFu) == (1u << 1))) return 0;
+    unsigned char ser[65];
+    const int r = amd_call(nullptr, 0, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_ec_pubkey_convert_batch(e, res, ser, compressed ? S2K_PK_COMPRESSED : S2K_PK_FULL, nullptr, (const unsigned char*)pubkey, S2K_PK_OBJECT, 1);
+    });
+    if (r) { memcpy(output, ser, compressed ? 33 : 65); *outputlen = compressed ? 33 : 65; }
+    return r;
+}
+// src/secp256k1.c:723 -- pubkey is read and written; zeroed when it does not load
+extern "C" int secp256k1_ec_pubkey_negate_amd(const void* ctx, void* pubkey) {
+    (void)ctx;
+    unsigned char in[64];
+    if (pubkey) memcpy(in, pubkey, 64);
+    return amd_one("secp256k1_ec_pubkey_negate_amd", pubkey != nullptr, pubkey, 64, true, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_ec_pubkey_negate_batch(e, res, (unsigned char*)pubkey, S2K_PK_OBJECT, nullptr, in, S2K_PK_OBJECT, 1);
+    });
+}
+// src/secp256k1.c:810 -- pubkey is read and written; zeroed on failure (:821 clears it before the product is tried)
+extern "C" int secp256k1_ec_pubkey_tweak_mul_amd(const void* ctx, void* pubkey, const unsigned char* tweak32) {
+    (void)ctx;
+    unsigned char in[64];
+    if (pubkey) memcpy(in, pubkey, 64);
+    return amd_one("secp256k1_ec_pubkey_tweak_mul_amd", pubkey && tweak32, pubkey, 64, true, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_ec_pubkey_tweak_mul_batch(e, res, (unsigned char*)pubkey, S2K_PK_OBJECT, nullptr, in, S2K_PK_OBJECT, tweak32, 1);
+    });
+}
+// src/secp256k1.c:843 -- out is zeroed before n and the pointers are looked at; the objects the pointers name are gathered first (out may be one of them)
+extern "C" int secp256k1_ec_pubkey_combine_amd(const void* ctx, void* out, const void* const* ins, size_t n) {
+    (void)ctx;
+    bool ins_ok = ins && n >= 1;
+    for (size_t i = 0; ins_ok && i < n; i++) ins_ok = ins[i] != nullptr;
+    std::vector<unsigned char> keys;
+    if (out && ins_ok) { keys.resize(64 * n); for (size_t i = 0; i < n; i++) memcpy(&keys[64 * i], ins[i], 64); }
+    return amd_one("secp256k1_ec_pubkey_combine_amd", out != nullptr, out, 64, ins_ok, [&](s2k_engine* e, int32_t* res) {
+        const uint64_t off[2] = {0, n};
+        return secp256k1_ec_pubkey_combine_batch(e, res, (unsigned char*)out, S2K_PK_OBJECT, nullptr, keys.data(), S2K_PK_OBJECT, off, 1);
+    });
+}
+// src/modules/extrakeys/main_impl.h:22 -- the object is zeroed first
+extern "C" int secp256k1_xonly_pubkey_parse_amd(const void* ctx, void* pubkey, const unsigned char* input32) {
+    (void)ctx;
+    return amd_one("secp256k1_xonly_pubkey_parse_amd", pubkey != nullptr, pubkey, 64, input32 != nullptr, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_ec_pubkey_convert_batch(e, res, (unsigned char*)pubkey, S2K_PK_OBJECT, nullptr, input32, S2K_PK_XONLY, 1);
+    });
+}
+// src/modules/extrakeys/main_impl.h:44 -- output32 is zeroed first
+extern "C" int secp256k1_xonly_pubkey_serialize_amd(const void* ctx, unsigned char* output32, const void* pubkey) {
+    (void)ctx;
+    return amd_one("secp256k1_xonly_pubkey_serialize_amd", output32 != nullptr, output32, 32, pubkey != nullptr, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_ec_pubkey_convert_batch(e, res, output32, S2K_PK_XONLY, nullptr, (const unsigned char*)pubkey, S2K_PK_OBJECT, 1);
+    });
+}
+// src/modules/extrakeys/main_impl.h:99 -- nothing is written where the key does not load (the reference returns in front of its stores)
+extern "C" int secp256k1_xonly_pubkey_from_pubkey_amd(const void* ctx, void* xonly_pubkey, int* pk_parity, const void* pubkey) {
+    (void)ctx;
+    if (!amd_args("secp256k1_xonly_pubkey_from_pubkey_amd", xonly_pubkey && pubkey)) return 0;
+    unsigned char obj[64], par = 0;
+    const int r = amd_call(nullptr, 0, [&](s2k_engine* e, int32_t* res) {
+        return secp256k1_ec_pubkey_convert_batch(e, res, obj, S2K_PK_XONLY_OBJECT, &par, (const unsigned char*)pubkey, S2K_PK_OBJECT, 1);
+    });
+    if (r) { memcpy(xonly_pubkey, obj, 64); if (pk_parity) *pk_parity = par; }
+    return r;
+}
 // src/modules/generator/main_impl.h:250 -- gen receives a secp256k1_generator object (the kernels live in engine_generator.hip)
 extern "C" int secp256k1_generator_generate_amd(const void* ctx, void* gen, const unsigned char* key32) {
     (void)ctx;
@@ -981,6 +1063,9 @@ extern "C" int s2k_engine_set_option(s2k_engine* e, int option, long value) {
     case S2K_OPT_MUSIG_SUM_FANIN:
         if (value < 2 || value > 64) return s2k_fail_arg("s2k_engine_set_option", "S2K_OPT_MUSIG_SUM_FANIN: 2 .. 64");
         e->musig_sum_fanin = (int)value; return 1;
+    case S2K_OPT_PUBKEY_FOLD_FANIN:
+        if (value < 2 || value > 64) return s2k_fail_arg("s2k_engine_set_option", "S2K_OPT_PUBKEY_FOLD_FANIN: 2 .. 64");
+        e->pubkey_fold_fanin = (int)value; return 1;
     case S2K_OPT_S2C_FUSED: e->s2c_fused = value != 0; return 1;
     case S2K_OPT_ELLSWIFT_MAX_ATTEMPTS:
         if (value < 1 || value > 256) return s2k_fail_arg("s2k_engine_set_option", "S2K_OPT_ELLSWIFT_MAX_ATTEMPTS: 1 .. 256");
@@ -1312,6 +1397,22 @@ extern "C" int secp256k1_xonly_pubkey_tweak_add_check_batch_group(s2k_group* g, 
     return group_by_items(g, n, {{results, sizeof(int32_t) * n}}, [=](s2k_engine* e, size_t lo, size_t hi) {
         return secp256k1_xonly_pubkey_tweak_add_check_batch(e, results + lo, tweaked32 + 32 * lo, parities + lo, internal_keys + kb * lo, key_format, tweaks32 + 32 * lo, hi - lo);
     });
+}
+// (split by item index; every engine multiplies its share into its slices of out and parities_out)
+extern "C" int secp256k1_ec_pubkey_tweak_mul_batch_group(s2k_group* g, int32_t* results, unsigned char* out, int out_format, unsigned char* parities_out,
+                                                         const unsigned char* keys, int key_format, const unsigned char* tweaks32, size_t n) {
+    const char* who = "secp256k1_ec_pubkey_tweak_mul_batch_group";
+    if (!g || g->eng.empty()) return s2k_fail(who, "null group");
+    if (n == 0) return 1;
+    if (!results || !out || !keys || !tweaks32) return s2k_fail_arg(who, "illegal argument (ARG_CHECK)");
+    if (out_format < S2K_PK_XONLY || out_format > S2K_PK_XONLY_OBJECT || key_format < S2K_PK_XONLY || key_format > S2K_PK_AFFINE) return s2k_fail_arg(who, "unknown out_format / key_format");
+    const size_t ob = pubkey_bytes(out_format), kb = pubkey_bytes(key_format);
+    auto per_engine = [=](s2k_engine* e, size_t lo, size_t hi) {
+        return secp256k1_ec_pubkey_tweak_mul_batch(e, results + lo, out + ob * lo, out_format, parities_out ? parities_out + lo : nullptr, keys + kb * lo, key_format,
+                                                   tweaks32 + 32 * lo, hi - lo);
+    };
+    if (!parities_out) return group_by_items(g, n, {{results, sizeof(int32_t) * n}, {out, ob * n}}, per_engine);
+    return group_by_items(g, n, {{results, sizeof(int32_t) * n}, {out, ob * n}, {parities_out, n}}, per_engine);
 }
 // One sum over the group.  Per engine i: its slice's scalars / points (device memory of engine i's GPU when `resident`, host memory
 // otherwise); the generator term goes with slice 0.  The result comes back to the host (r_xy 64 bytes, *r_inf).

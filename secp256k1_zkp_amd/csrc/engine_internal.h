@@ -1,7 +1,7 @@
 // engine_internal.h -- what the translation units of the gfx950 batch-verification engine share (see include/secp256k1_zkp_amd.h):
 // the engine object, the per-device table pool, error plumbing, workspace carving and the host functions one kernel family offers the others.
 //
-// The library is eighteen translation units, one per kernel family, compiled separately (hipcc --offload-arch=gfx950 -O3 -fPIC -c) and linked
+// The library is nineteen translation units, one per kernel family, compiled separately (hipcc --offload-arch=gfx950 -O3 -fPIC -c) and linked
 // into one shared object (see __graft_entry__.build):
 //   engine_core.hip        table construction, the per-device pool and generator-table cache, engine lifecycle / options / groups,
 //                          s2k_ecmult_batch, BIP-340, the single-item `_amd` forms and the `_group` forms of every family
@@ -22,6 +22,7 @@
 //   engine_ellswift.hip    ElligatorSwift decoding and encoding of public keys (ellswift.h)
 //   engine_schnorr_all.hip one-verdict batch verification of BIP-340 signatures as a single multi-scalar multiplication (schnorr_all.h)
 //   engine_bppp_all.hip    one-verdict batch verification of BP++ norm arguments over one generator set as a single multi-scalar multiplication (bppp_all.h)
+//   engine_pubkey.hip      public-key conversion between the five encodings, negation, tweak-mul and combine (pubkey.h)
 // What a family does around its kernels is engine_lanes.h (host code only, included by the units that use it): lanes_run behind the
 // `_dev` forms of the one-item-per-lane families, stage_open / stage_close behind the host-buffer forms of every family (each staged
 // buffer named once, beside the device part's own workspace where there is one; the stager orders its uploads behind the engine's last
@@ -148,6 +149,7 @@ struct s2k_engine {
     struct { int c, T, chunk, two_pass, one_pass, bin_plain, no_small, T2, old_tail, slice_r, slice_lds, slice_maxc, run_major; } msm_diag;
     size_t msm_max_terms_opt;  // S2K_OPT_MSM_MAX_TERMS: sums with more terms go as several launches whose partial sums add (0: the 32-bit reference limit)
     int musig_sum_fanin;       // S2K_OPT_MUSIG_SUM_FANIN: partials one lane of the MuSig summing kernel folds per pass (0: the default, 64)
+    int pubkey_fold_fanin;     // S2K_OPT_PUBKEY_FOLD_FANIN: keys one lane of the first pass of secp256k1_ec_pubkey_combine_batch folds, and partials per lane of its further passes (0: the default, 16)
     int s2c_fused;             // S2K_OPT_S2C_FUSED: anti-exfil host verification as one kernel instead of the default chain of two (engine_s2c.hip)
     int ellswift_max_attempts; // S2K_OPT_ELLSWIFT_MAX_ATTEMPTS: the bound of the ElligatorSwift encode loop (engine_ellswift.hip; default and maximum 256)
     u32* ha_pin; size_t ha_pin_words;   // pinned: the chain states of the half-aggregate randomizer hash, walked on the host (host_sha256.h)
@@ -289,3 +291,9 @@ struct ha_host_src { const unsigned char* aggsig; const unsigned char* pks; int 
 size_t ha_ws_bytes(const s2k_engine* e, size_t n);
 int ha_launch(s2k_engine* e, hipStream_t st, ws_carver& c, int32_t* d_res, const unsigned char* d_pk, int pk_format, const unsigned char* d_msg, size_t n,
               const unsigned char* d_agg, const ha_host_src* host = nullptr, const u32* d_states_in = nullptr);
+// ---- the segmented sum of 28-word partials (engine_musig_agg.hip; the plan is musig_agg.h's musig_agg_plan_sum) -------------------------------
+// d_off: the plan's offset arrays as they are; pass q reads a when q is even and b when it is odd, and writes the other.  Runs passes
+// first_pass .. p.passes - 1 (a family whose own kernel is pass 0 says 1) in sub-range launches; *result is where the nseg sums are.
+struct musig_agg_sum_plan;
+struct agg_sum_bufs { u64* d_off; u32* a; u32* b; };
+int agg_sum_launch(s2k_engine* e, hipStream_t st, const musig_agg_sum_plan& p, const agg_sum_bufs& s, unsigned fanin, const u32** result, size_t first_pass = 0);

@@ -107,15 +107,16 @@ static int agg_offsets_ok(const char* who, const uint64_t* off, size_t n) {
 }
 typedef musig_agg_sum_plan agg_sum_plan;      // (musig_agg.h)
 static size_t agg_sum_ws(const agg_sum_plan& p) { return ws_need({8 * p.offs.size(), (size_t)4 * MUSIG_AGG_GEJ_WORDS * p.cap, (size_t)4 * MUSIG_AGG_GEJ_WORDS * p.cap}); }
-struct agg_sum_bufs { u64* d_off; u32* a; u32* b; };
 static agg_sum_bufs agg_sum_carve(ws_carver& w, const agg_sum_plan& p) {
     agg_sum_bufs s; s.d_off = w.take<u64>(p.offs.size()); s.a = w.take<u32>((size_t)MUSIG_AGG_GEJ_WORDS * p.cap); s.b = w.take<u32>((size_t)MUSIG_AGG_GEJ_WORDS * p.cap);
     return s;
 }
-// runs the passes over the partials in s.a; *result is where the nseg sums are
-static int agg_sum_launch(s2k_engine* e, hipStream_t st, const agg_sum_plan& p, const agg_sum_bufs& s, unsigned fanin, const u32** result) {
+// runs the passes from `first_pass` on (engine_internal.h: also offered to engine_pubkey.hip, whose own kernel is pass 0); pass q reads
+// s.a when q is even and s.b when it is odd.  *result is where the nseg sums are.
+int agg_sum_launch(s2k_engine* e, hipStream_t st, const agg_sum_plan& p, const agg_sum_bufs& s, unsigned fanin, const u32** result, size_t first_pass) {
     u32* in = s.a; u32* out = s.b;
-    for (size_t q = 0; q < p.passes; q++) {
+    if (first_pass & 1) std::swap(in, out);
+    for (size_t q = first_pass; q < p.passes; q++) {
         const u64* in_off = s.d_off + q * (p.nseg + 1); const u64* out_off = in_off + p.nseg + 1;
         const size_t total = (size_t)p.offs[(q + 1) * (p.nseg + 1) + p.nseg];
         for (size_t j0 = 0; j0 < total; j0 += e->max_lanes) {

@@ -131,11 +131,17 @@ S2K_HD void musig_agg_fold_lane(u32* out28, const u32* in28, u64 first, u64 coun
 }
 
 // output j of a pass: segment k of the pass's output offsets, folding inputs in_off[k] + fanin * (j - out_off[k]) ... of that segment
-S2K_HD void musig_agg_sum_item(u32* out, const u32* in, const u64* in_off, const u64* out_off, u64 nseg, u32 fanin, u64 j) {
+// (the range alone, for a pass that reads something other than partials: pubkey.h's first pass over key bytes)
+S2K_HD void musig_agg_sum_range(u64& first, u64& count, const u64* in_off, const u64* out_off, u64 nseg, u32 fanin, u64 j) {
     const u64 k = musig_agg_segment(out_off, nseg, j);
-    const u64 first = in_off[k] + (u64)fanin * (j - out_off[k]);
+    first = in_off[k] + (u64)fanin * (j - out_off[k]);
     const u64 left = in_off[k + 1] > first ? in_off[k + 1] - first : 0;
-    musig_agg_fold_lane(out + (size_t)MUSIG_AGG_GEJ_WORDS * j, in, first, left < fanin ? left : fanin);
+    count = left < fanin ? left : fanin;
+}
+S2K_HD void musig_agg_sum_item(u32* out, const u32* in, const u64* in_off, const u64* out_off, u64 nseg, u32 fanin, u64 j) {
+    u64 first, count;
+    musig_agg_sum_range(first, count, in_off, out_off, nseg, fanin, j);
+    musig_agg_fold_lane(out + (size_t)MUSIG_AGG_GEJ_WORDS * j, in, first, count);
 }
 
 // a Jacobian sum to affine through the wave-shared inversion: EVERY lane of the wavefront comes through here.  `want`: the lane has a
