@@ -530,6 +530,43 @@ S2K_API int secp256k1_ec_pubkey_combine_batch(s2k_engine* e, int32_t* results, u
 S2K_API int secp256k1_ec_pubkey_combine_batch_dev(s2k_engine* e, void* stream, int32_t* results, unsigned char* out, int out_format, unsigned char* parities_out,
                                                   const unsigned char* keys, int key_format, const uint64_t* key_off_host, size_t n_sets);
 
+/* ---- SHA-256, tagged hashes and BIP-340 with a message length per item -------------------------------------------------
+ * PUBLIC DATA ONLY.  The 32-byte digests that the verifiers of this header take (msghash32, msgs32, data32, the 32-byte messages
+ * of BIP-340) are in practice SHA-256, double SHA-256 or tagged hashes of preimages of a few hundred bytes: these calls make them
+ * on the GPU, one message per lane, so that a _dev verifier reads them where they were written.
+ *   s2k_sha256_batch:              out32_i = SHA256(m_i) (rounds 1) or SHA256(SHA256(m_i)) (rounds 2); any other rounds is
+ *                                  S2K_STATUS_ILLEGAL_ARGUMENT
+ *   secp256k1_tagged_sha256_batch: out32_i = SHA256(SHA256(tag) | SHA256(tag) | m_i), byte for byte what
+ *                                  secp256k1_tagged_sha256(ctx, out32_i, tag, taglen, m_i, len_i) writes (src/secp256k1.c:869-881).
+ *                                  tag is HOST memory in both forms: its midstate is computed on the host and passed by value.
+ * out32 is n*32 bytes.  The items:
+ *   msg_off == NULL   item i is msgs[i*msglen .. (i+1)*msglen); msglen 0 is legal.
+ *   msg_off != NULL   uint64_t[n+1]; item i is msgs[msg_off[i] .. msg_off[i+1]) and msglen is ignored (the sig_off convention of the
+ *                     DER forms).  msg_off[0] need not be 0.
+ * Only bytes inside an item are read: a buffer may end with its last item.
+ * The host forms refuse offsets that decrease (S2K_STATUS_ILLEGAL_ARGUMENT, nothing written) and upload only the bytes
+ * [msg_off[0], msg_off[n]).  The _dev forms take msgs, msg_off and out32 in HBM and cannot look at the offsets: an item with
+ * msg_off[i+1] < msg_off[i] gets 32 zero bytes -- never the digest of the empty message -- and none of its bytes is read; its
+ * neighbours are not affected.  n == 0 returns 1 and touches nothing; a NULL out32, tag or msgs is S2K_STATUS_ILLEGAL_ARGUMENT.
+ * A wavefront runs as long as its longest message: sort by length first where lengths differ by orders of magnitude. */
+S2K_API int s2k_sha256_batch(s2k_engine* e, unsigned char* out32, const unsigned char* msgs, const uint64_t* msg_off, size_t msglen, int rounds, size_t n);
+S2K_API int s2k_sha256_batch_dev(s2k_engine* e, void* stream, unsigned char* out32, const unsigned char* msgs, const uint64_t* msg_off, size_t msglen, int rounds,
+                                 size_t n);
+S2K_API int secp256k1_tagged_sha256_batch(s2k_engine* e, unsigned char* out32, const unsigned char* tag, size_t taglen, const unsigned char* msgs,
+                                          const uint64_t* msg_off, size_t msglen, size_t n);
+S2K_API int secp256k1_tagged_sha256_batch_dev(s2k_engine* e, void* stream, unsigned char* out32, const unsigned char* tag, size_t taglen, const unsigned char* msgs,
+                                              const uint64_t* msg_off, size_t msglen, size_t n);
+/* secp256k1_tagged_sha256 with the reference's argument list (include/secp256k1.h), one item on the default engine; ctx is ignored.
+ * Returns 1; 0 with S2K_STATUS_ILLEGAL_ARGUMENT for a NULL hash32, tag or msg (the reference's ARG_CHECKs, msglen 0 included). */
+S2K_API int secp256k1_tagged_sha256_amd(const void* ctx, unsigned char* hash32, const unsigned char* tag, size_t taglen, const unsigned char* msg, size_t msglen);
+/* results[i] = secp256k1_schnorrsig_verify(ctx, sig64_i, msg_i, msg_off[i+1] - msg_off[i], pubkey_i): secp256k1_schnorrsig_verify_batch
+ * with a message length per item.  msgs and msg_off as above, msg_off required; sigs, pubkeys and pk_format as in
+ * secp256k1_schnorrsig_verify_batch.  A decreasing pair of offsets: the host form refuses the call, the _dev form gives that item 0. */
+S2K_API int secp256k1_schnorrsig_verify_batch_var(s2k_engine* e, int32_t* results, const unsigned char* sigs, const unsigned char* msgs, const uint64_t* msg_off,
+                                                  const unsigned char* pubkeys, int pk_format, size_t n);
+S2K_API int secp256k1_schnorrsig_verify_batch_var_dev(s2k_engine* e, void* stream, int32_t* results, const unsigned char* sigs, const unsigned char* msgs,
+                                                      const uint64_t* msg_off, const unsigned char* pubkeys, int pk_format, size_t n);
+
 /* ---- asset generators ----------------------------------------------------------------------------------------------
  * PUBLIC INPUTS ONLY: nothing below is constant time.  A blind handed to these functions is treated as public data (the
  * reference's generate_blinded and pedersen_commit are secret-key paths; here they serve explicit amounts, blind 0, and the

@@ -89,6 +89,13 @@ SIGNATURES = {
     "secp256k1_xonly_pubkey_parse_amd": (_c.c_int, [_vp, _vp, _vp]),
     "secp256k1_xonly_pubkey_serialize_amd": (_c.c_int, [_vp, _vp, _vp]),
     "secp256k1_xonly_pubkey_from_pubkey_amd": (_c.c_int, [_vp, _vp, _vp, _vp]),
+    "s2k_sha256_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _c.c_int, _sz]),
+    "s2k_sha256_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _c.c_int, _sz]),
+    "secp256k1_tagged_sha256_batch": (_c.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz]),
+    "secp256k1_tagged_sha256_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz]),
+    "secp256k1_tagged_sha256_amd": (_c.c_int, [_vp, _vp, _vp, _sz, _vp, _sz]),
+    "secp256k1_schnorrsig_verify_batch_var": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _sz]),
+    "secp256k1_schnorrsig_verify_batch_var_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _sz]),
     "secp256k1_generator_generate_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "secp256k1_generator_generate_batch_dev": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "secp256k1_generator_parse_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _sz]),

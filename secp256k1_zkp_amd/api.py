@@ -729,6 +729,104 @@ class Engine:
         self._check(self._lib.secp256k1_ec_pubkey_combine_batch_dev(self._h, stream, _dp(results), _dp(out), out_format, _dp(parities_out), _dp(keys), key_format, _p(key_off),
                                                                     key_off.size - 1), "secp256k1_ec_pubkey_combine_batch_dev")
 
+    # ---- SHA-256, double SHA-256 and secp256k1_tagged_sha256 (secp256k1.c:869-881) of one message per lane; BIP-340 with a length per item ----
+    @staticmethod
+    def _msg_items(what, msgs, msg_off, msglen, n):
+        """host arrays -> (msgs, msg_off or None, msglen, n).  Exactly one of msg_off / msglen; decreasing offsets are left to the library."""
+        if (msg_off is None) == (msglen is None):
+            raise ValueError(f"{what}: give exactly one of msg_off and msglen")
+        if msgs is None:
+            raise ValueError(f"{what}: missing array")
+        msgs = _u8(msgs)
+        if msg_off is not None:
+            msg_off = np.ascontiguousarray(msg_off, dtype=np.uint64).reshape(-1)
+            if msg_off.size == 0:
+                raise S2KError(f"{what}: msg_off is empty (it has n + 1 entries)")
+            if int(msg_off.max()) > msgs.size:
+                raise ValueError(f"{what}: msg_off points behind the data ({msgs.size} bytes)")
+            return msgs, msg_off, 0, msg_off.size - 1
+        msglen = int(msglen)
+        if msglen < 0:
+            raise ValueError(f"{what}: msglen must not be negative")
+        if n is None:
+            if msglen == 0:
+                raise ValueError(f"{what}: msglen 0 needs n")
+            n = msgs.size // msglen
+        _need(what + " msgs", msgs, msglen * n)
+        return msgs, None, msglen, n
+
+    @staticmethod
+    def _msg_items_dev(what, msg_off, msglen, msgs, n):
+        if (msg_off is None) == (msglen is None):
+            raise ValueError(f"{what}: give exactly one of msg_off and msglen")
+        if msg_off is not None:
+            if msg_off.numel() == 0:
+                raise S2KError(f"{what}: msg_off is empty (it has n + 1 entries)")
+            return 0, msg_off.numel() - 1 if n is None else n
+        msglen = int(msglen)
+        if msglen < 0 or (n is None and msglen == 0):
+            raise ValueError(f"{what}: msglen must not be negative, and msglen 0 needs n")
+        return msglen, msgs.numel() // msglen if n is None else n
+
+    def sha256_batch(self, msgs, msg_off=None, msglen=None, rounds=1, n=None):
+        """-> digests[n, 32]: SHA256 (rounds 1) or SHA256 of SHA256 (rounds 2) of every item.  msglen: n items of msglen bytes back to back;
+        msg_off: uint64[n+1], item i is msgs[msg_off[i] .. msg_off[i+1]).  Exactly one of the two."""
+        msgs, msg_off, msglen, n = self._msg_items("sha256_batch", msgs, msg_off, msglen, n)
+        out = np.zeros((n, 32), np.uint8)
+        pad = msgs if msgs.size else np.zeros(1, np.uint8)
+        self._check(self._lib.s2k_sha256_batch(self._h, _p(out), _p(pad), _p(msg_off), msglen, int(rounds), n), "s2k_sha256_batch")
+        return out
+
+    def sha256_batch_dev(self, out32, msgs, msg_off=None, msglen=None, rounds=1, n=None, stream=None):
+        """every array in HBM (torch tensors; msg_off: int64 / uint64 offsets[n+1]).  An item whose offsets decrease gets 32 zero bytes."""
+        msglen, n = self._msg_items_dev("sha256_batch_dev", msg_off, msglen, msgs, n)
+        self._check(self._lib.s2k_sha256_batch_dev(self._h, stream, _dp(out32), _dp(msgs), _dp(msg_off), msglen, int(rounds), n), "s2k_sha256_batch_dev")
+
+    def tagged_sha256_batch(self, tag, msgs, msg_off=None, msglen=None, n=None):
+        """-> digests[n, 32]: secp256k1_tagged_sha256(tag, item) of every item; tag: bytes.  Items as in sha256_batch."""
+        if tag is None:
+            raise ValueError("tagged_sha256_batch: missing tag")
+        tag = bytes(tag)
+        msgs, msg_off, msglen, n = self._msg_items("tagged_sha256_batch", msgs, msg_off, msglen, n)
+        out = np.zeros((n, 32), np.uint8)
+        pad = msgs if msgs.size else np.zeros(1, np.uint8)
+        self._check(self._lib.secp256k1_tagged_sha256_batch(self._h, _p(out), tag, len(tag), _p(pad), _p(msg_off), msglen, n), "secp256k1_tagged_sha256_batch")
+        return out
+
+    def tagged_sha256_batch_dev(self, out32, tag, msgs, msg_off=None, msglen=None, n=None, stream=None):
+        """tag: bytes on the host; every array in HBM (torch tensors)"""
+        if tag is None:
+            raise ValueError("tagged_sha256_batch_dev: missing tag")
+        tag = bytes(tag)
+        msglen, n = self._msg_items_dev("tagged_sha256_batch_dev", msg_off, msglen, msgs, n)
+        self._check(self._lib.secp256k1_tagged_sha256_batch_dev(self._h, stream, _dp(out32), tag, len(tag), _dp(msgs), _dp(msg_off), msglen, n),
+                    "secp256k1_tagged_sha256_batch_dev")
+
+    def schnorrsig_verify_batch_var(self, sigs, msgs, msg_off, pubkeys, pk_format=0):
+        """results[i] = secp256k1_schnorrsig_verify(sig_i, msgs[msg_off[i] .. msg_off[i+1]), pubkey_i): a message length per item"""
+        if pk_format not in (0, 1):
+            raise ValueError("schnorrsig_verify_batch_var: pk_format must be 0 (32-byte x-only keys) or 1 (64-byte objects)")
+        if msg_off is None or sigs is None or pubkeys is None:
+            raise ValueError("schnorrsig_verify_batch_var: missing array")
+        msgs, msg_off, _, n = self._msg_items("schnorrsig_verify_batch_var", msgs, msg_off, None, None)
+        sigs = _u8(sigs); pubkeys = _u8(pubkeys)
+        _need("schnorrsig_verify_batch_var sigs", sigs, 64 * n); _need("schnorrsig_verify_batch_var pubkeys", pubkeys, (64 if pk_format else 32) * n)
+        res = np.zeros(n, np.int32)
+        pad = msgs if msgs.size else np.zeros(1, np.uint8)
+        self._check(self._lib.secp256k1_schnorrsig_verify_batch_var(self._h, _p(res), _p(sigs), _p(pad), _p(msg_off), _p(pubkeys), pk_format, n),
+                    "secp256k1_schnorrsig_verify_batch_var")
+        return res
+
+    def schnorrsig_verify_batch_var_dev(self, results, sigs, msgs, msg_off, pubkeys, pk_format=0, n=None, stream=None):
+        """every array in HBM (torch tensors; msg_off: int64 / uint64 offsets[n+1]).  An item whose offsets decrease gets 0."""
+        if pk_format not in (0, 1):
+            raise ValueError("schnorrsig_verify_batch_var_dev: pk_format must be 0 or 1")
+        if msg_off is None:
+            raise ValueError("schnorrsig_verify_batch_var_dev: msg_off is required")
+        _, n = self._msg_items_dev("schnorrsig_verify_batch_var_dev", msg_off, None, msgs, n)
+        self._check(self._lib.secp256k1_schnorrsig_verify_batch_var_dev(self._h, stream, _dp(results), _dp(sigs), _dp(msgs), _dp(msg_off), _dp(pubkeys), pk_format, n),
+                    "secp256k1_schnorrsig_verify_batch_var_dev")
+
     # ---- secp256k1_ellswift_decode and secp256k1_ellswift_encode (modules/ellswift/main_impl.h:470-483, :393-420), batched ----
     def ellswift_decode(self, ell64, out_format=1):
         """ell64: n*64 ElligatorSwift encodings -> out[n, 32 / 64 / 33]: out_format 0: ser32(x), 1: secp256k1_pubkey objects, 2: compressed keys.

@@ -20,7 +20,7 @@ UNITS = ["engine_core", "engine_rangeproof", "engine_msm", "engine_msm_many", "e
 # exactly like the seven above.
 # (tests/test_cpu_musig_agg.py::test_abi_is_declared pins "engine_musig_agg" as the LAST entry and tests/test_cpu_schnorr_all.py the last two:
 # later units go in front of "engine_schnorr_all")
-UNITS_ADDED = ["engine_whitelist", "engine_tweak", "engine_generator", "engine_adaptor", "engine_musig", "engine_halfagg_batch", "engine_s2c", "engine_ellswift", "engine_bppp_all", "engine_pubkey", "engine_schnorr_all", "engine_musig_agg"]
+UNITS_ADDED = ["engine_whitelist", "engine_tweak", "engine_generator", "engine_adaptor", "engine_musig", "engine_halfagg_batch", "engine_s2c", "engine_ellswift", "engine_bppp_all", "engine_pubkey", "engine_hash", "engine_schnorr_all", "engine_musig_agg"]
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-fvisibility=hidden"]
 DEFAULT_LIB = os.path.join(HERE, "libsecp256k1_zkp_amd.so")
 

@@ -989,6 +989,14 @@ extern "C" int secp256k1_xonly_pubkey_from_pubkey_amd(const void* ctx, void* xon
     if (r) { memcpy(xonly_pubkey, obj, 64); if (pk_parity) *pk_parity = par; }
     return r;
 }
+// src/secp256k1.c:869 -- nothing is written where an argument check fails (the kernels live in engine_hash.hip)
+extern "C" int secp256k1_tagged_sha256_amd(const void* ctx, unsigned char* hash32, const unsigned char* tag, size_t taglen, const unsigned char* msg, size_t msglen) {
+    (void)ctx;
+    return amd_one("secp256k1_tagged_sha256_amd", hash32 && tag && msg, [&](s2k_engine* e, int32_t* res) {
+        *res = 1;
+        return secp256k1_tagged_sha256_batch(e, hash32, tag, taglen, msg, nullptr, msglen, 1);
+    });
+}
 // src/modules/generator/main_impl.h:250 -- gen receives a secp256k1_generator object (the kernels live in engine_generator.hip)
 extern "C" int secp256k1_generator_generate_amd(const void* ctx, void* gen, const unsigned char* key32) {
     (void)ctx;

@@ -1,7 +1,7 @@
 // engine_internal.h -- what the translation units of the gfx950 batch-verification engine share (see include/secp256k1_zkp_amd.h):
 // the engine object, the per-device table pool, error plumbing, workspace carving and the host functions one kernel family offers the others.
 //
-// The library is nineteen translation units, one per kernel family, compiled separately (hipcc --offload-arch=gfx950 -O3 -fPIC -c) and linked
+// The library is twenty translation units, one per kernel family, compiled separately (hipcc --offload-arch=gfx950 -O3 -fPIC -c) and linked
 // into one shared object (see __graft_entry__.build):
 //   engine_core.hip        table construction, the per-device pool and generator-table cache, engine lifecycle / options / groups,
 //                          s2k_ecmult_batch, BIP-340, the single-item `_amd` forms and the `_group` forms of every family
@@ -23,6 +23,7 @@
 //   engine_schnorr_all.hip one-verdict batch verification of BIP-340 signatures as a single multi-scalar multiplication (schnorr_all.h)
 //   engine_bppp_all.hip    one-verdict batch verification of BP++ norm arguments over one generator set as a single multi-scalar multiplication (bppp_all.h)
 //   engine_pubkey.hip      public-key conversion between the five encodings, negation, tweak-mul and combine (pubkey.h)
+//   engine_hash.hip        SHA-256, double SHA-256 and tagged hashes of one message per lane, BIP-340 with a message length per item (hash_batch.h)
 // What a family does around its kernels is engine_lanes.h (host code only, included by the units that use it): lanes_run behind the
 // `_dev` forms of the one-item-per-lane families, stage_open / stage_close behind the host-buffer forms of every family (each staged
 // buffer named once, beside the device part's own workspace where there is one; the stager orders its uploads behind the engine's last
